@@ -14,11 +14,18 @@ walking — then W further untimed warm-up steps, then K timed steps, no renderi
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 1000 --warmup 500       # the same, launched from outside
 
-A short timed region (K < 500: the driver's ``--steps 20``) is one launch of a few milliseconds, so ``repeats`` of
-them run back to back (the gait continuing) inside one barrier + synchronize bracket and the mean region time is
-reported; ``config.repeats`` says how many.  The line is marked
+``--steps K`` is the number of timed steps.  ``--repeats R`` runs R such K-step regions back to back (the gait
+continuing) inside one barrier + synchronize bracket and reports the mean region time (``--repeats 0``: enough regions
+for about 1000 timed steps); ``config.repeats`` says how many.  The line is marked
 ``"valid": false`` and the exit code is 3 if the timed region was not contact-rich stepping (mean contacts < 1
 or no solver iterations: flies in free fall), if the state went non-finite, or if contacts overflowed.
+
+A plain run sets up, settles, times the K steps and prints the line.  ``--full`` adds what takes runs of its own: the
+CPU baseline (``cpu_baseline``), the workload re-run under ``rocprofv3 --pmc`` for the roofline's live counters, and the
+short runs of the other BASELINE configs (``other_configs``); ``--no-cpu-baseline``, ``--no-live-counters`` and
+``--no-other-configs`` drop one of them again.  ``--dump-outputs DIR`` writes what the last timed step computed (state,
+poses, actuator forces, sensors and, where the workload has them, the vision / odor / observation outputs) as
+``DIR/<name>.npy`` in float32; the inputs are seeded, so two builds can be compared output for output.
 
 One process per GPU; worlds are independent, so each rank steps its own shard (``--scaling weak``: 4096 per
 GPU; ``--scaling strong``: 4096 in total) and the only inter-GPU traffic is an RCCL all-gather of the
@@ -63,7 +70,7 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=500,
                     help="untimed steps under the control table AFTER the unconditional settle")
-    ap.add_argument("--repeats", type=int, default=0,
+    ap.add_argument("--repeats", type=int, default=1,
                     help="how often the K-step timed region is repeated (0 = auto: about 1000 timed steps in total)")
     ap.add_argument("--worlds-per-gpu", type=int, default=4096)
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
@@ -102,13 +109,19 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-flavour", action="store_true",
                     help="step the engine of the reference's CPU class (flygym_amd.Simulation: Newton + option/noslip_iterations = 5, "
                          "mujoco_globals.yaml:15) instead of the batched class's, which strips the pass (BASELINE config 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own (N = 1): the CPU baseline, the live rocprofv3 counters of the "
+                         "roofline and the other BASELINE configs; a plain run times the headline workload only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-live-counters", action="store_true",
-                    help="do not re-run the workload under rocprofv3 --pmc after the timed region (N = 1): roofline.traffic / "
-                         ".issue then come from the committed passes under profiles/ and say so")
+                    help="--full without re-running the workload under rocprofv3 --pmc after the timed region (N = 1): "
+                         "roofline.traffic / .issue then come from the committed passes under profiles/ and say so")
     ap.add_argument("--cpu-steps", type=int, default=200000)
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="do not append the short runs of BASELINE configs 1, 3, 4 and 5 (`other_configs`, N = 1 only)")
+                    help="--full without the short runs of BASELINE configs 1, 3, 4 and 5 (`other_configs`, N = 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, at most 64 MB in "
+                         "all: a fixed, seeded sample of the worlds when the batch is larger)")
     return ap.parse_args(argv)
 
 
@@ -201,6 +214,30 @@ def algorithmic_flops(nv, nb, ncon, iters):
     return kin + inertia + collision + bias + solves * aba + iters * (newton + ncon * 50) + nv * 20
 
 
+DUMP_FIELDS = ("qpos", "qvel", "qacc", "actuator_force", "sensordata", "seg_xpos", "seg_xquat", "site_xpos")
+DUMP_BUDGET_BYTES = 60 * 10**6     # the .npy headers stay well inside 64 MB
+
+
+def dump_outputs(directory, arrays, n_worlds, suffix="", budget=DUMP_BUDGET_BYTES):
+    """``--dump-outputs``: write ``arrays`` ({name: (tensor, world axis)}) as ``directory/<name><suffix>.npy`` in float32
+    (empty ones, e.g. the sites of a model without any, are left out).  Above ``budget`` bytes in all, every array keeps the
+    same fixed, seeded sample of the worlds (in world order)."""
+    import torch
+
+    arrays = {name: ta for name, ta in arrays.items() if ta[0].numel()}
+    total = sum(4 * t.numel() for t, _ in arrays.values())
+    keep = None
+    if total > budget:
+        k = max(1, n_worlds * budget // total)
+        keep = torch.as_tensor(np.sort(np.random.default_rng(0).choice(n_worlds, k, replace=False)))
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, (t, axis) in arrays.items():
+        if keep is not None:
+            t = t.index_select(axis, keep.to(t.device))
+        np.save(out / f"{name}{suffix}.npy", t.detach().float().cpu().numpy())
+
+
 def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -256,7 +293,8 @@ def live_counters(spl, kernel, launches=6, budget_s=240.0, passes=None):
         return None, "rocprofv3 not on PATH"
     if any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ):
         return None, "already running under a profiler"
-    drop = {"--steps": 1, "--warmup": 1, "--repeats": 1, "--gpus": 1, "--steps-per-launch": 1, "--cpu-steps": 1, "--no-cpu-baseline": 0}
+    drop = {"--steps": 1, "--warmup": 1, "--repeats": 1, "--gpus": 1, "--steps-per-launch": 1, "--cpu-steps": 1, "--no-cpu-baseline": 0,
+            "--full": 0, "--dump-outputs": 1}
     argv, skip = [], 0
     for a in sys.argv[1:]:
         if skip:
@@ -408,7 +446,7 @@ def run(args, primary=True):
         rng = np.random.default_rng(0)     # S = 3 sources, D = 2 dims, seeded within +-20 mm
         src = rng.uniform(-20, 20, (3, 3)); src[:, 2] = rng.uniform(0.5, 3.0, 3)
         odor = OdorSensors(sim, fly.name, src, rng.uniform(0.1, 1.0, (3, 2)))
-    see, frames, vision_out = None, None, None
+    see, frames, vision_out, odor_out = None, None, None, None
     if args.vision == "resample":
         from flygym_amd.sensors import RAW_IMG_HEIGHT as H, RAW_IMG_WIDTH as W, Retina
 
@@ -491,7 +529,8 @@ def run(args, primary=True):
             vision_out = see()
             ev2[k].record()
         if odor is not None:
-            odor.get_odor_intensities()
+            nonlocal odor_out
+            odor_out = odor.get_odor_intensities()
         if gather is not None:
             gather.tick(sim.field("qpos"), sim.field("qvel"), sim.field("actuator_force"), sim.field("sensordata"))
 
@@ -549,6 +588,17 @@ def run(args, primary=True):
         rccl_ranks = int((probe > 0).sum().item()) if dist.get_world_size() == world_size else 0
     valid = finite and mean_contacts >= 1.0 and mean_iters > 0.0 and overflow_steps == 0 \
         and abs(steps_seen - float(total_worlds) * args.steps * repeats) < 0.5
+    if primary and args.dump_outputs:
+        # what a caller of the timed path receives after its last step: every rank writes its own shard
+        outputs = {k: (sim.field(k), 0) for k in DUMP_FIELDS}
+        if vision_out is not None:
+            outputs["vision_readings"] = (vision_out, 0)
+        if odor_out is not None:
+            outputs["odor_intensities"] = (odor_out, 0)
+        if ring is not None:
+            outputs["observations"] = (ring, 1)        # (recorded steps of the last launch, worlds, 270)
+        dump_outputs(args.dump_outputs, outputs, n_local, "" if world_size == 1 else f".rank{rank}",
+                     DUMP_BUDGET_BYTES // world_size)
 
     out = None
     if rank == 0:
@@ -566,9 +616,11 @@ def run(args, primary=True):
         traffic, issue = traffic_model(n_local, spl, args)
         traffic_source = "profiles/hbm_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command run by the builder, fitted per world and per step)" if traffic is not None else None
         issue_source = "profiles/hbm_traffic.json (rocprofv3 --pmc SQ_* passes of this command run by the builder)" if issue else None
-        live, live_note = None, ("off (--no-live-counters)" if args.no_live_counters else "N > 1: committed passes" if world_size > 1
+        live_on = args.full and not args.no_live_counters
+        live, live_note = None, ("off (a plain run: --full measures them)" if not args.full else "off (--no-live-counters)" if not live_on
+                                 else "N > 1: committed passes" if world_size > 1
                                  else "vision run: the live passes go to the retina kernel (`roofline`), this block uses the committed ones")
-        if primary and not args.no_live_counters and world_size == 1 and see is None:
+        if primary and live_on and world_size == 1 and see is None:
             live, live_note = live_counters(spl, "nmf_step_kernel")
         if live:
             # MI355X_MICROARCH.md, HBM section: FETCH_SIZE / WRITE_SIZE count KiB; FETCH_SIZE under-reports wide reads by 2x on
@@ -677,7 +729,7 @@ def run(args, primary=True):
                 vt = rec.get("traffic_bytes_per_eye_frame", 0) * 2 * n_local or None
             vt_source = "profiles/vision_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command run by the builder)" if vt else None
             vlive = None
-            if primary and not args.no_live_counters and world_size == 1 and args.vision == "resample":
+            if primary and live_on and world_size == 1 and args.vision == "resample":
                 vlive, vnote = live_counters(spl, "nmf_retina_stream_kernel", passes=LIVE_PASSES[:2])
                 if vlive:      # wide coalesced 16-byte reads: the x2 of the guide's gfx950 correction applies in full
                     vt, vt_source = 1024.0 * (2.0 * vlive["FETCH_SIZE"] + vlive["WRITE_SIZE"]), vnote
@@ -707,7 +759,7 @@ def run(args, primary=True):
                                        "physics_kernel_ms_per_tick": ms}
             if args.vision == "render":
                 out["config"]["vision"]["rays_per_ommatidium"] = args.eye_rays or "every pixel of the cell (pixel-exact)"
-        if primary and not args.no_cpu_baseline and world_size == 1:   # reported at N=1 only
+        if primary and args.full and not args.no_cpu_baseline and world_size == 1:   # reported at N=1 only
             n_rows = min(n_local, host_cores())
             rows = np.ascontiguousarray(table[:n_rows, :, :42].cpu().numpy())
             out["cpu_baseline"] = cpu_baseline(sim.model.to_blob(), rows, np.arange(42, dtype=np.int32), settle_neutral,
@@ -775,7 +827,8 @@ def main():
     if args.gpus > 1 and os.environ.get("WORLD_SIZE") is None:
         raise SystemExit(self_spawn(args))
     out, valid, rank = run(args, primary=True)
-    if out is not None and out["n_gpus"] == 1 and not args.no_other_configs and not any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ):
+    if out is not None and out["n_gpus"] == 1 and args.full and not args.no_other_configs \
+            and not any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ):
         out["other_configs"], secs = other_configs(args)
         out["other_configs_seconds"] = secs
     if rank == 0:

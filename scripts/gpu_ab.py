@@ -36,7 +36,7 @@ import tempfile
 from pathlib import Path
 
 ROOT = Path(os.environ.get("GRAFT_REPO_ROOT") or Path(__file__).resolve().parents[1])
-BENCH = [sys.executable, str(ROOT / "bench.py"), "--no-cpu-baseline", "--no-live-counters"]
+BENCH = [sys.executable, str(ROOT / "bench.py"), "--repeats", "0", "--no-cpu-baseline", "--no-live-counters"]   # ~1000 timed steps per line
 DEFAULT_LINES = ["", "--steps 20 --warmup 5", "--workload replay --steps 20 --warmup 5"]
 COUNTERS = "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_IFETCH SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_ANY"
 

@@ -1,14 +1,16 @@
 #!/bin/bash
-# the whole GPU suite, then the bench as the driver runs it (with other_configs) and at its default arguments
+# the whole GPU suite, then the bench as the driver runs it (--full: with other_configs) and at its default arguments
+# usage: scripts/gpu_suite.sh LOG_DIR
+OUT=${1:?usage: scripts/gpu_suite.sh LOG_DIR}
 cd $GRAFT_REPO_ROOT
 export PYTHONPATH=$GRAFT_REPO_ROOT
-mkdir -p gpurun_out
-( timeout 1500 python -m pytest tests -m gpu -q 2>&1 | grep -v Warn | tail -40 ) > gpurun_out/r6_pytest.log
-( timeout 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 ) > gpurun_out/r6_smoke.log
-python bench.py --no-cpu-baseline --no-live-counters --steps 20 --warmup 5 > gpurun_out/r6_bench_driver.log 2>&1
-python bench.py --no-cpu-baseline --no-live-counters --no-other-configs > gpurun_out/r6_bench_default.log 2>&1
-tail -30 gpurun_out/r6_pytest.log; cat gpurun_out/r6_smoke.log
-for f in gpurun_out/r6_bench_driver.log gpurun_out/r6_bench_default.log; do grep '^{"metric"' $f | python -c "
+mkdir -p "$OUT"
+( timeout 1500 python -m pytest tests -m gpu -q 2>&1 | grep -v Warn | tail -40 ) > "$OUT/r6_pytest.log"
+( timeout 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 ) > "$OUT/r6_smoke.log"
+python bench.py --full --repeats 0 --no-cpu-baseline --no-live-counters --steps 20 --warmup 5 > "$OUT/r6_bench_driver.log" 2>&1
+python bench.py --no-cpu-baseline --no-live-counters --no-other-configs > "$OUT/r6_bench_default.log" 2>&1
+tail -30 "$OUT/r6_pytest.log"; cat "$OUT/r6_smoke.log"
+for f in "$OUT/r6_bench_driver.log" "$OUT/r6_bench_default.log"; do grep '^{"metric"' $f | python -c "
 import sys, json
 for l in sys.stdin:
     d = json.loads(l); c = d['config']
