@@ -243,41 +243,71 @@ int upload_i(nmf_batch* b, const char* name, void* slot) {
   return upload(b, a->i, static_cast<const int**>(slot));
 }
 
-int alloc_field(nmf_batch* b, int field, int width, float** out) {
+// A device buffer of `count` T that lives as long as the batch, zeroed unless `zero` is false
+template <class T>
+int alloc_dev(nmf_batch* b, size_t count, T** out, bool zero = true) {
   void* p = nullptr;
-  size_t bytes = sizeof(float) * (size_t)b->n_worlds * (size_t)(width > 0 ? width : 1);
-  HIP_OK(hipMalloc(&p, bytes));
-  HIP_OK(hipMemset(p, 0, bytes));
+  if (hipMalloc(&p, sizeof(T) * count) != hipSuccess) return fail("nmf_batch_create: out of device memory");
   b->allocs.push_back(p);
-  b->fields[field] = (float*)p;
-  b->widths[field] = width;
-  *out = (float*)p;
+  *out = (T*)p;
+  if (zero) HIP_OK(hipMemset(p, 0, sizeof(T) * count));
   return 0;
+}
+
+int alloc_field(nmf_batch* b, int field, int width, float** out) {
+  if (alloc_dev(b, (size_t)b->n_worlds * (size_t)(width > 0 ? width : 1), out) != 0) return -1;
+  b->fields[field] = *out;
+  b->widths[field] = width;
+  return 0;
+}
+
+template <class T> struct TopoTag { using type = T; };
+
+// The kernel family of a batch (nmf_batch::topo) as its topology type: calls f(TopoTag<TP>{}), false for a family this build
+// left out (NMF_TOPO_MASK).  The one place the host side lists the families.
+template <class F>
+bool with_topo(int topo, F&& f) {
+  switch (topo) {
+#if NMF_HAS_TOPO(0)
+    case 0: f(TopoTag<nmf::FlyTopo>{}); return true;
+#endif
+#if NMF_HAS_TOPO(1)
+    case 1: f(TopoTag<nmf::FlyTopoActive>{}); return true;
+#endif
+#if NMF_HAS_TOPO(2)
+    case 2: f(TopoTag<nmf::TreeTopoSmall>{}); return true;
+#endif
+#if NMF_HAS_TOPO(3)
+    case 3: f(TopoTag<nmf::TreeTopo>{}); return true;
+#endif
+#if NMF_HAS_TOPO(4)
+    case 4: f(TopoTag<nmf::FlyTopoBio>{}); return true;
+#endif
+#if NMF_HAS_TOPO(5)
+    case 5: f(TopoTag<nmf::FlyTopoAll>{}); return true;
+#endif
+    default: return false;
+  }
+}
+
+// The stepping kernel of a family for a tethered (weld), terrain or plain world; nullptr if the build has no such family
+const void* step_kernel(int topo, bool weld, bool terrain) {
+  const void* fn = nullptr;
+  with_topo(topo, [&](auto tag) {
+    using TP = typename decltype(tag)::type;
+    fn = weld ? reinterpret_cast<const void*>(&nmf::nmf_step_kernel<TP, true>)
+              : terrain ? reinterpret_cast<const void*>(&nmf::nmf_step_kernel<nmf::Terrain<TP>, false>)
+                        : reinterpret_cast<const void*>(&nmf::nmf_step_kernel<TP, false>);
+  });
+  return fn;
 }
 
 int launch_reset(nmf_batch* b, const uint8_t* mask_dev, hipStream_t stream) {
   DEVICE_GUARD(b);
-  dim3 grid((unsigned)b->n_worlds), block(nmf::kWave);
-#define NMF_RESET_TOPO(K, TOPO) if (b->topo == K) hipLaunchKernelGGL((nmf::nmf_reset_kernel<TOPO>), grid, block, 0, stream, b->dm_dev, b->st, mask_dev);
-#if NMF_HAS_TOPO(0)
-  NMF_RESET_TOPO(0, nmf::FlyTopo)
-#endif
-#if NMF_HAS_TOPO(1)
-  NMF_RESET_TOPO(1, nmf::FlyTopoActive)
-#endif
-#if NMF_HAS_TOPO(2)
-  NMF_RESET_TOPO(2, nmf::TreeTopoSmall)
-#endif
-#if NMF_HAS_TOPO(3)
-  NMF_RESET_TOPO(3, nmf::TreeTopo)
-#endif
-#if NMF_HAS_TOPO(4)
-  NMF_RESET_TOPO(4, nmf::FlyTopoBio)
-#endif
-#if NMF_HAS_TOPO(5)
-  NMF_RESET_TOPO(5, nmf::FlyTopoAll)
-#endif
-#undef NMF_RESET_TOPO
+  with_topo(b->topo, [&](auto tag) {
+    hipLaunchKernelGGL((nmf::nmf_reset_kernel<typename decltype(tag)::type>), dim3((unsigned)b->n_worlds), dim3(nmf::kWave), 0, stream,
+                       b->dm_dev, b->st, mask_dev);
+  });
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -328,59 +358,63 @@ int launch(nmf_batch* b, const nmf::ReplayArgs& rp, int n_steps, hipStream_t str
     b->st.order = b->order_buf;
     if (policy < 0) b->st.sched = b->sched_buf;
   }
-  const bool weld = b->dm.weld_active != 0, terrain = b->dm.terrain_type != 0;
-#define NMF_LAUNCH(TOPO, WELD) hipLaunchKernelGGL((nmf::nmf_step_kernel<TOPO, WELD>), grid, block, b->lds_pad, stream, b->dm_dev, b->st, rp, n_steps)
-#define NMF_LAUNCH_TOPO(K, TOPO) if (b->topo == K) { if (weld) NMF_LAUNCH(TOPO, true); else if (terrain) NMF_LAUNCH(nmf::Terrain<TOPO>, false); else NMF_LAUNCH(TOPO, false); }
-#if NMF_HAS_TOPO(0)
-  NMF_LAUNCH_TOPO(0, nmf::FlyTopo)
-#endif
-#if NMF_HAS_TOPO(1)
-  NMF_LAUNCH_TOPO(1, nmf::FlyTopoActive)
-#endif
-#if NMF_HAS_TOPO(2)
-  NMF_LAUNCH_TOPO(2, nmf::TreeTopoSmall)
-#endif
-#if NMF_HAS_TOPO(3)
-  NMF_LAUNCH_TOPO(3, nmf::TreeTopo)
-#endif
-#if NMF_HAS_TOPO(4)
-  NMF_LAUNCH_TOPO(4, nmf::FlyTopoBio)
-#endif
-#if NMF_HAS_TOPO(5)
-  NMF_LAUNCH_TOPO(5, nmf::FlyTopoAll)
-#endif
-#undef NMF_LAUNCH_TOPO
-#undef NMF_LAUNCH
+  // the batch's stepping kernel (step_kernel): nmf_step_kernel(const DevModel*, DevState, ReplayArgs, int)
+  const nmf::DevModel* dm = b->dm_dev;
+  nmf::ReplayArgs rp_arg = rp;
+  void* args[] = {&dm, &b->st, &rp_arg, &n_steps};
+  (void)hipLaunchKernel(b->step_fn, grid, block, args, b->lds_pad, stream);
   HIP_OK(hipGetLastError());
   return 0;
 }
 
-}  // namespace
-
-namespace {
-template <class T> struct TopoTag { using type = T; };
 // Development overrides from the process environment — honoured only under NMF_ALLOW_ENV=1 (the one getenv gate of this
 // library): a stray NMF_* variable in a user's shell never changes what a batch runs.
 const char* dev_env(const char* name) {
   static const bool allowed = [] { const char* e = getenv("NMF_ALLOW_ENV"); return e && atoi(e) != 0; }();
   return allowed ? getenv(name) : nullptr;
 }
-}  // namespace
 
-extern "C" nmf_batch* nmf_batch_create(const nmf_model* model, int n_worlds, int device) {
-  return nmf_batch_create_ex(model, n_worlds, device, nullptr);
+// nmf_batch_options (0 = the library's default) with the development overrides written over it: an override beats an option.
+// chunk_div is a double (the override's precision) and 0 unless given: an option <= 1 is no request, an override >= 1 is one.
+struct Options {
+  int solver = 0, sched = 0, order = 0, max_chunks = 0, min_chunk_steps = 0, order_every = 0, rest_slow = 0, flies_per_cu = 0;
+  double chunk_div = 0.0;
+};
+
+Options read_options(const nmf_batch_options& in) {
+  Options o;
+  o.solver = in.solver; o.sched = in.sched; o.order = in.order; o.max_chunks = in.max_chunks; o.min_chunk_steps = in.min_chunk_steps;
+  o.order_every = in.order_every; o.rest_slow = in.rest_slow; o.flies_per_cu = in.flies_per_cu;
+  if (in.chunk_div > 1.f) o.chunk_div = in.chunk_div;
+  // NMF_SOLVER = primal | nohist | nofallback (default: contact-space solve with the active-set history); NMF_SCHED = chunks
+  // (default) | plain; NMF_ORDER = auto (default) | inorder | costliest | none | policy (the option codes of include/nmf.h)
+  if (const char* e = dev_env("NMF_SOLVER")) {
+    const std::string v(e);
+    o.solver = v == "primal" ? 1 : v == "nohist" ? 2 : v == "nofallback" ? 4 : 0;
+  }
+  if (const char* e = dev_env("NMF_SCHED")) o.sched = std::string(e) == "plain" ? 1 : 0;
+  if (const char* e = dev_env("NMF_ORDER")) {
+    const std::string v(e);
+    o.order = v == "inorder" ? 1 : v == "costliest" ? 2 : v == "none" ? 3 : v == "policy" ? 4 : 0;
+  }
+  if (const char* e = dev_env("NMF_ORDER_EVERY")) o.order_every = std::max(1, atoi(e));
+  if (const char* e = dev_env("NMF_MAX_CHUNKS")) o.max_chunks = std::max(1, std::min(16, atoi(e)));
+  if (const char* e = dev_env("NMF_CHUNK_DIV")) o.chunk_div = std::max(1.0, atof(e));
+  if (const char* e = dev_env("NMF_MIN_CHUNK_STEPS")) o.min_chunk_steps = std::max(1, atoi(e));
+  if (const char* e = dev_env("NMF_FLIES_PER_CU")) o.flies_per_cu = atoi(e);
+  // NMF_DISABLE_REST_FAST: diagnostic switch, forces the table-driven level passes (tests cover both paths)
+  if (dev_env("NMF_DISABLE_REST_FAST")) o.rest_slow = 1;
+  return o;
 }
 
-extern "C" nmf_batch* nmf_batch_create_ex(const nmf_model* model, int n_worlds, int device, const nmf_batch_options* options) {
-  g_err.clear();
-  nmf_batch_options opt{};
-  if (options) {
-    if (options->struct_size < (int32_t)sizeof(int32_t) || options->struct_size > (int32_t)sizeof(nmf_batch_options)) { fail("nmf_batch_create_ex: options->struct_size does not match this library"); return nullptr; }
-    memcpy(&opt, options, (size_t)options->struct_size);
-  }
-  if (!model) { fail("nmf_batch_create: null model"); return nullptr; }
-  if (n_worlds <= 0) { fail("nmf_batch_create: n_worlds must be positive"); return nullptr; }
+// The skeleton's kernel family and, for the families with tree sweeps, the tree tables in breadth-first order
+struct Skeleton {
   int topo = -1;
+  std::vector<int> tree_body, child_start, child_count, lvl_start;    // lvl_start: starts of levels 0..maxd and the end
+};
+
+int classify_skeleton(const nmf_model* model, Skeleton& sk) {
+  int& topo = sk.topo;
   if (model->star[0] == 1 && model->star[1] == 6 && model->star[2] == 11 && model->star[3] == 8) topo = 0;
   if (model->star[0] == 1 && model->star[1] == 6 && model->star[2] == 7 && model->star[3] == 4) topo = 1;
   if (topo >= 0) {  // the chain-star kernels hard-wire the per-leg hinge layout (and 48 controls); anything else takes the tree kernel
@@ -414,21 +448,20 @@ extern "C" nmf_batch* nmf_batch_create_ex(const nmf_model* model, int n_worlds, 
     }
   }
   // anything else (custom skeletons): the general-tree kernel, up to 72 bodies / 216 dofs
-  std::vector<int> tree_body, child_start, child_count, lvl_start;
+  std::vector<int> &tree_body = sk.tree_body, &child_start = sk.child_start, &child_count = sk.child_count, &lvl_start = sk.lvl_start;
   if (topo < 0 || topo >= 4) {
     if (topo < 0) topo = model->nv <= nmf::TreeTopoSmall::NV && model->nu <= nmf::TreeTopoSmall::kCtrl ? 2 : 3;
     const HostArray* bp = model->find("body_parent");
     const HostArray* dn = model->find("body_dofnum");
     const HostArray* gb = model->find("geom_body");
-    if (!bp || !dn || !gb || model->nb > nmf::TreeTopo::NB || model->nv > nmf::TreeTopo::NV || dn->i.empty() || dn->i[0] != 6) {
-      fail("nmf_batch_create: the general-tree kernel takes a free-floating root and up to 72 bodies / 216 dofs"); return nullptr;
-    }
+    if (!bp || !dn || !gb || model->nb > nmf::TreeTopo::NB || model->nv > nmf::TreeTopo::NV || dn->i.empty() || dn->i[0] != 6)
+      return fail("nmf_batch_create: the general-tree kernel takes a free-floating root and up to 72 bodies / 216 dofs");
     const int nb = model->nb;
     if (in_tree.empty()) in_tree.assign((size_t)nb, 1);
     for (int bb = 1; bb < nb; ++bb)
-      if (bp->i[(size_t)bb] < 0 || bp->i[(size_t)bb] >= bb) { fail("nmf_batch_create: bodies must be ordered parents first"); return nullptr; }
+      if (bp->i[(size_t)bb] < 0 || bp->i[(size_t)bb] >= bb) return fail("nmf_batch_create: bodies must be ordered parents first");
     for (size_t g = 1; g < gb->i.size(); ++g)
-      if (gb->i[g] < gb->i[g - 1]) { fail("nmf_batch_create: contact geoms must be ordered by body"); return nullptr; }
+      if (gb->i[g] < gb->i[g - 1]) return fail("nmf_batch_create: contact geoms must be ordered by body");
     // breadth-first order: level by level, the children of a body contiguous
     std::vector<int> depth((size_t)nb, 0);
     int maxd = 0;
@@ -436,7 +469,7 @@ extern "C" nmf_batch* nmf_batch_create_ex(const nmf_model* model, int n_worlds, 
       depth[(size_t)bb] = depth[(size_t)bp->i[(size_t)bb]] + 1;
       if (in_tree[(size_t)bb]) maxd = std::max(maxd, depth[(size_t)bb]);
     }
-    if (maxd + 2 > 18) { fail("nmf_batch_create: kinematic tree deeper than 16 levels"); return nullptr; }
+    if (maxd + 2 > 18) return fail("nmf_batch_create: kinematic tree deeper than 16 levels");
     tree_body.push_back(0); lvl_start.push_back(0);
     child_start.assign((size_t)nb, 0); child_count.assign((size_t)nb, 0);
     for (int lv = 0; lv <= maxd; ++lv) {
@@ -447,16 +480,20 @@ extern "C" nmf_batch* nmf_batch_create_ex(const nmf_model* model, int n_worlds, 
         child_start[(size_t)par] = (int)tree_body.size();
         for (int bb = 1; bb < nb; ++bb) if (bp->i[(size_t)bb] == par && in_tree[(size_t)bb]) { tree_body.push_back(bb); child_count[(size_t)par]++; }
       }
-      if (k1 - k0 > nmf::kWave) { fail("nmf_batch_create: more than 64 bodies on one tree level"); return nullptr; }
+      if (k1 - k0 > nmf::kWave) return fail("nmf_batch_create: more than 64 bodies on one tree level");
     }
     // lvl_start has maxd + 2 entries: starts of levels 0..maxd and the end
   }
-  if (model->ng > 2 * nmf::kWave) { fail("nmf_batch_create: more than 128 contact geoms"); return nullptr; }
-  if (model->nu > (topo >= 2 ? nmf::TreeTopo::kCtrl : nmf::kMaxCtrl)) { fail("nmf_batch_create: too many actuators (48 for the leg skeletons, 224 otherwise)"); return nullptr; }
-  DeviceGuard guard(device);            // allocations and the first reset run on `device`; the caller's device comes back on return
-  if (guard.err != hipSuccess) { fail("nmf_batch_create: hipSetDevice failed (no MI355X visible?)"); return nullptr; }
-  auto* b = new nmf_batch();
-  b->model = model; b->n_worlds = n_worlds; b->device = device; b->topo = topo;
+  if (model->ng > 2 * nmf::kWave) return fail("nmf_batch_create: more than 128 contact geoms");
+  if (model->nu > (topo >= 2 ? nmf::TreeTopo::kCtrl : nmf::kMaxCtrl)) return fail("nmf_batch_create: too many actuators (48 for the leg skeletons, 224 otherwise)");
+  return 0;
+}
+
+// DevModel: the model's scalars and arrays, the tree tables and the solver option bits, uploaded to b->dm_dev
+int fill_model(nmf_batch* b, const Skeleton& sk, const Options& opt) {
+  const nmf_model* model = b->model;
+  const int topo = sk.topo;
+  const std::vector<int> &tree_body = sk.tree_body, &child_start = sk.child_start, &child_count = sk.child_count, &lvl_start = sk.lvl_start;
   nmf::DevModel& d = b->dm;
   d.nb = model->nb; d.nv = model->nv; d.nq = model->nq; d.nu = model->nu; d.ng = model->ng;
   d.nseg = model->nseg; d.nsite = model->nsite; d.nsensor = model->nsensor; d.max_iter = model->max_iter;
@@ -473,7 +510,7 @@ extern "C" nmf_batch* nmf_batch_create_ex(const nmf_model* model, int n_worlds, 
     for (int k = 0; k < 5; ++k) d.weld_solimp[k] = scalar("weld_params", 9 + k);
     for (int k = 0; k < 2; ++k) d.weld_invweight[k] = scalar("weld_params", 14 + k); }
   { const HostArray* so = model->find("sem_options");
-    if (!so || !so->is_int || so->i.size() < 5) { delete b; fail("nmf_batch_create: model lacks sem_options"); return nullptr; }
+    if (!so || !so->is_int || so->i.size() < 5) return fail("nmf_batch_create: model lacks sem_options");
     d.sem_terrain_walls = so->i[4];
     d.sem_pyramid_plain = so->i[0]; d.sem_adhesion_fused = so->i[1]; d.sem_sensor_contact_frame = so->i[2];
     d.sem_max_hull_contacts = so->i[3] >= 1 && so->i[3] <= 4 ? so->i[3] : 4; }
@@ -518,8 +555,7 @@ extern "C" nmf_batch* nmf_batch_create_ex(const nmf_model* model, int n_worlds, 
       const HostArray* dn = model->find("body_dofnum");
       const HostArray* da = model->find("body_dofadr");
       const int nl = (int)lvl_start.size() - 2;                 // levels below the root
-      // NMF_DISABLE_REST_FAST: diagnostic switch, forces the table-driven level passes (tests cover both paths)
-      bool fast = da && nl <= nmf::kRestLevels && !opt.rest_slow && !dev_env("NMF_DISABLE_REST_FAST");
+      bool fast = da && nl <= nmf::kRestLevels && !opt.rest_slow;
       std::vector<int> pack((size_t)nmf::kRestLevels * 16, -1);
       for (int lv = 1; fast && lv <= nl; ++lv) {
         const int k0 = lvl_start[(size_t)lv], k1 = lvl_start[(size_t)lv + 1];
@@ -540,162 +576,129 @@ extern "C" nmf_batch* nmf_batch_create_ex(const nmf_model* model, int n_worlds, 
   if (const HostArray* os2 = model->find("opt_solver")) { if (os2->i.size() > 1) d.noslip_iter = os2->i[1]; }
   d.max_contacts = nmf::kMaxCon;
   d.solver_flags = opt.solver & 7;
-  if (const char* e = dev_env("NMF_SOLVER")) {      // primal | nohist | nofallback (default: contact-space solve with the active-set history)
-    const std::string v(e);
-    d.solver_flags = v == "primal" ? 1 : v == "nohist" ? 2 : v == "nofallback" ? 4 : 0;
-  }
-  if (rc == 0) {
-    void* p = nullptr;
-    if (hipMalloc(&p, sizeof(nmf::DevModel)) != hipSuccess ||
-        hipMemcpy(p, &d, sizeof(nmf::DevModel), hipMemcpyHostToDevice) != hipSuccess) { fail("nmf_batch_create: model upload failed"); rc = -1; }
-    else { b->allocs.push_back(p); b->dm_dev = (nmf::DevModel*)p; }
-  }
+  if (rc != 0) return rc;
+  void* p = nullptr;
+  if (hipMalloc(&p, sizeof(nmf::DevModel)) != hipSuccess) return fail("nmf_batch_create: model upload failed");
+  b->allocs.push_back(p); b->dm_dev = (nmf::DevModel*)p;
+  if (hipMemcpy(p, &d, sizeof(nmf::DevModel), hipMemcpyHostToDevice) != hipSuccess) return fail("nmf_batch_create: model upload failed");
+  return 0;
+}
+
+// DevState: the per-world fields and the stepping kernel's scratch
+int alloc_state(nmf_batch* b) {
+  const nmf_model* model = b->model;
+  const size_t n_worlds = (size_t)b->n_worlds;
   nmf::DevState& st = b->st;
-  st.n_worlds = n_worlds;
-  rc |= alloc_field(b, NMF_QPOS, model->nq, &st.qpos);
-  rc |= alloc_field(b, NMF_QVEL, model->nv, &st.qvel);
-  rc |= alloc_field(b, NMF_CTRL, model->nu, &st.ctrl);
-  rc |= alloc_field(b, NMF_QACC_WARMSTART, model->nv, &st.qacc_ws);
-  rc |= alloc_field(b, NMF_SEG_XPOS, model->nseg * 3, &st.seg_xpos);
-  rc |= alloc_field(b, NMF_SEG_XQUAT, model->nseg * 4, &st.seg_xquat);
-  rc |= alloc_field(b, NMF_SITE_XPOS, model->nsite * 3, &st.site_xpos);
-  rc |= alloc_field(b, NMF_ACTUATOR_FORCE, model->nu, &st.actuator_force);
-  rc |= alloc_field(b, NMF_SENSORDATA, 96, &st.sensordata);
-  rc |= alloc_field(b, NMF_TIME, 1, &st.time);
-  rc |= alloc_field(b, NMF_STATS, 8, &st.stats);
-  rc |= alloc_field(b, NMF_QACC, model->nv, &st.qacc);
-  rc |= alloc_field(b, NMF_COST, 1, &st.cost);
-  { float* p = nullptr; rc |= alloc_field(b, NMF_STATS_SUM, 16, &p); st.stats_sum = reinterpret_cast<unsigned int*>(p); }   // uint32 counters
-  rc |= alloc_field(b, NMF_CONTACT_GEOM, nmf::kMaxCon, &st.contact_geom);
-  rc |= alloc_field(b, NMF_ACT, model->nu, &st.act);
-  {
-    void* p = nullptr;
-    if (hipMalloc(&p, sizeof(int) * (size_t)n_worlds) == hipSuccess) { b->allocs.push_back(p); b->order_buf = (int*)p; }
-    else rc |= fail("nmf_batch_create: out of device memory");
-    p = nullptr;
-    if (hipMalloc(&p, sizeof(nmf::ChunkSched)) == hipSuccess) {
-      (void)hipMemset(p, 0, sizeof(nmf::ChunkSched));
-      b->allocs.push_back(p); b->csched_buf = (nmf::ChunkSched*)p;
-    } else rc |= fail("nmf_batch_create: out of device memory");
-    p = nullptr;
-    b->handoff_stride = (model->nq + 2 * model->nv + model->nu + 6 + nmf::kActHistWords + 63) / 64 * 64;      // state, controls, clock + 5 running sums, active-set history
-    if (hipMalloc(&p, sizeof(unsigned long long) * (size_t)n_worlds * (size_t)b->handoff_stride) == hipSuccess) {
-      (void)hipMemset(p, 0, sizeof(unsigned long long) * (size_t)n_worlds * (size_t)b->handoff_stride);   // tag 0 = no launch's
-      b->allocs.push_back(p); b->handoff_buf = (unsigned long long*)p;
-    } else rc |= fail("nmf_batch_create: out of device memory");
-    p = nullptr;
-    if (hipMalloc(&p, sizeof(unsigned int) * (size_t)n_worlds * nmf::kActHistWords) == hipSuccess) {
-      (void)hipMemset(p, 0, sizeof(unsigned int) * (size_t)n_worlds * nmf::kActHistWords);
-      b->allocs.push_back(p); st.act_hist = (unsigned int*)p;
-    } else rc |= fail("nmf_batch_create: out of device memory");
-    st.dual_scratch = nullptr;
-    if (topo == 5) {       // ALL_POSSIBLE: the contact-space solve's leg factors live in HBM, one block per workgroup of a launch (<= n_worlds)
-      p = nullptr;
-      if (hipMalloc(&p, sizeof(float) * (size_t)n_worlds * nmf::kDualScratchFloats) == hipSuccess) { b->allocs.push_back(p); st.dual_scratch = (float*)p; }
-      else rc |= fail("nmf_batch_create: out of device memory");
+  st.n_worlds = b->n_worlds;
+  float* stats_sum = nullptr;
+  b->handoff_stride = (model->nq + 2 * model->nv + model->nu + 6 + nmf::kActHistWords + 63) / 64 * 64;      // state, controls, clock + 5 running sums, active-set history
+  if (alloc_field(b, NMF_QPOS, model->nq, &st.qpos) || alloc_field(b, NMF_QVEL, model->nv, &st.qvel) ||
+      alloc_field(b, NMF_CTRL, model->nu, &st.ctrl) || alloc_field(b, NMF_QACC_WARMSTART, model->nv, &st.qacc_ws) ||
+      alloc_field(b, NMF_SEG_XPOS, model->nseg * 3, &st.seg_xpos) || alloc_field(b, NMF_SEG_XQUAT, model->nseg * 4, &st.seg_xquat) ||
+      alloc_field(b, NMF_SITE_XPOS, model->nsite * 3, &st.site_xpos) || alloc_field(b, NMF_ACTUATOR_FORCE, model->nu, &st.actuator_force) ||
+      alloc_field(b, NMF_SENSORDATA, 96, &st.sensordata) || alloc_field(b, NMF_TIME, 1, &st.time) ||
+      alloc_field(b, NMF_STATS, 8, &st.stats) || alloc_field(b, NMF_QACC, model->nv, &st.qacc) || alloc_field(b, NMF_COST, 1, &st.cost) ||
+      alloc_field(b, NMF_STATS_SUM, 16, &stats_sum) ||        // uint32 counters
+      alloc_field(b, NMF_CONTACT_GEOM, nmf::kMaxCon, &st.contact_geom) || alloc_field(b, NMF_ACT, model->nu, &st.act) ||
+      alloc_dev(b, n_worlds, &b->order_buf, false) || alloc_dev(b, 1, &b->csched_buf) ||
+      alloc_dev(b, n_worlds * (size_t)b->handoff_stride, &b->handoff_buf) ||      // tag 0 = no launch's
+      alloc_dev(b, n_worlds * nmf::kActHistWords, &st.act_hist))
+    return -1;
+  st.stats_sum = reinterpret_cast<unsigned int*>(stats_sum);
+  st.dual_scratch = nullptr;
+  // ALL_POSSIBLE: the contact-space solve's leg factors live in HBM, one block per workgroup of a launch (<= n_worlds)
+  if (b->topo == 5 && alloc_dev(b, n_worlds * nmf::kDualScratchFloats, &st.dual_scratch, false)) return -1;
+  st.noslip_buf = nullptr;
+  // CPU flavour: scratch of the primal path's noslip pass (157 KB per world)
+  if (b->dm.noslip_iter > 0 && alloc_dev(b, n_worlds * nmf::kNoslipFloats, &st.noslip_buf)) return -1;
+  if (alloc_dev(b, 2, &b->clock_probe_buf) || alloc_dev(b, 1, &b->sched_buf)) return -1;
+  st.clock_probe = b->clock_probe_buf;
+  st.sched = nullptr;
+  st.order = nullptr;
+  return 0;
+}
+
+// The chunk plan and the world order of launch()
+void set_schedule(nmf_batch* b, const Options& opt) {
+  b->chunking = opt.sched != 1;
+  if (opt.order) b->order_policy = opt.order == 1 ? 0 : opt.order == 2 ? 1 : opt.order == 3 ? 2 : opt.order == 4 ? -1 : 3;
+  if (opt.order_every > 0) b->order_every = opt.order_every;
+  if (opt.max_chunks > 0) b->max_chunks = std::max(1, std::min(16, opt.max_chunks));
+  // (flat ground, leg-chain skeleton: a world's cost varies least and a step is cheapest against the hand-over — fewer, longer
+  // chunks; terrains and the full-body skeletons keep the halving plan: blocks 34.2 vs 32.4 M, ALL_BIOLOGICAL 30.7 vs 30.2 M)
+  // (and launches of more than 64 steps: 250-step launches 56.1 M halving, 54.5 M with 1.6)
+  // (round 5, one contact-space solve for every walking step: 1.5 / 1.6 / 1.7 / 1.8 / 2.0 = 56.7 / 56.6 / 56.7 / 56.6 / 55.8 M on 20-step
+  // launches, 58.7 / 58.9 / 59.2 / 59.0 / 58.9 M on 50-step ones)
+  b->chunk_div = (b->dm.terrain_type == 0 && b->topo < 2) ? 1.7 : 2.0;
+  b->chunk_div_short = true;
+  if (opt.chunk_div > 0.0) { b->chunk_div = opt.chunk_div; b->chunk_div_short = false; }
+  if (opt.min_chunk_steps > 0) b->min_chunk_steps = opt.min_chunk_steps;
+  // (activations live in HBM and are advanced in place every step by the lane that owns the actuator: a world's steps must stay
+  // on one workgroup within a launch — whole-launch work items for the models that have general actuators)
+  if (b->dm.act_general) b->chunking = false;
+}
+
+// The stepping kernel and its residency: flies (= single-wave workgroups) a CU holds at once, asked of the runtime for the
+// kernel this batch will launch (LDS- or register-limited, whichever binds); fallback = the LDS-limited figures of the
+// shipped build
+int pick_kernel(nmf_batch* b, const Options& opt) {
+  const int topo = b->topo, device = b->device;
+  int per_cu = topo < 2 ? 8 : (topo == 2 ? 4 : (topo == 3 ? 3 : (topo == 4 ? 8 : 5)));
+  const bool weld = b->dm.weld_active != 0, terrain = b->dm.terrain_type != 0;
+  if (weld && terrain) return fail("nmf_batch_create: a tethered world has no terrain");
+  const void* fn = step_kernel(topo, weld, terrain);
+  if (!fn) return fail("nmf_batch_create: this build of the library has no kernel for the model's skeleton (NMF_TOPO_MASK)");
+  int nblk = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, fn, nmf::kWave, 0) == hipSuccess && nblk > 0) per_cu = nblk;
+  b->step_fn = fn;
+  // options.flies_per_cu below the kernel's own residency: idle LDS per workgroup so that k workgroups fit a CU and k + 1 do
+  // not — as little of it as that takes (allocation granule 512 B), so the CU keeps LDS for another stream's kernel
+  const int want = opt.flies_per_cu;
+  hipFuncAttributes fa;
+  if (want > 0 && want < per_cu && hipFuncGetAttributes(&fa, fn) == hipSuccess) {
+    int lds_cu = 0;
+    if (hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, device) != hipSuccess || lds_cu <= 0) lds_cu = 160 * 1024;
+    const int granule = 512;
+    int per_wg = (lds_cu / (want + 1) / granule + 1) * granule;            // the smallest allocation of which want + 1 do not fit
+    if (per_wg * want <= lds_cu && per_wg > (int)fa.sharedSizeBytes) {
+      b->lds_pad = (unsigned)(per_wg - (int)fa.sharedSizeBytes);
+      int nblk2 = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk2, fn, nmf::kWave, b->lds_pad) == hipSuccess && nblk2 > 0) per_cu = std::min(per_cu, nblk2);
+      else per_cu = want;
     }
-    st.noslip_buf = nullptr;
-    if (d.noslip_iter > 0) {       // CPU flavour: scratch of the primal path's noslip pass (157 KB per world)
-      p = nullptr;
-      if (hipMalloc(&p, sizeof(float) * (size_t)n_worlds * nmf::kNoslipFloats) == hipSuccess) {
-        (void)hipMemset(p, 0, sizeof(float) * (size_t)n_worlds * nmf::kNoslipFloats);
-        b->allocs.push_back(p); st.noslip_buf = (float*)p;
-      } else rc |= fail("nmf_batch_create: out of device memory");
-    }
-    p = nullptr;
-    if (hipMalloc(&p, 2 * sizeof(unsigned long long)) == hipSuccess) {
-      (void)hipMemset(p, 0, 2 * sizeof(unsigned long long));
-      b->allocs.push_back(p); b->clock_probe_buf = (unsigned long long*)p;
-    } else rc |= fail("nmf_batch_create: out of device memory");
-    st.clock_probe = b->clock_probe_buf;
-    b->chunking = opt.sched != 1;
-    if (opt.order) b->order_policy = opt.order == 1 ? 0 : opt.order == 2 ? 1 : opt.order == 3 ? 2 : opt.order == 4 ? -1 : 3;
-    if (opt.order_every > 0) b->order_every = opt.order_every;
-    if (opt.max_chunks > 0) b->max_chunks = std::max(1, std::min(16, opt.max_chunks));
-    // (flat ground, leg-chain skeleton: a world's cost varies least and a step is cheapest against the hand-over — fewer, longer
-    // chunks; terrains and the full-body skeletons keep the halving plan: blocks 34.2 vs 32.4 M, ALL_BIOLOGICAL 30.7 vs 30.2 M)
-    // (and launches of more than 64 steps: 250-step launches 56.1 M halving, 54.5 M with 1.6)
-    // (round 5, one contact-space solve for every walking step: 1.5 / 1.6 / 1.7 / 1.8 / 2.0 = 56.7 / 56.6 / 56.7 / 56.6 / 55.8 M on 20-step
-    // launches, 58.7 / 58.9 / 59.2 / 59.0 / 58.9 M on 50-step ones)
-    b->chunk_div = (b->dm.terrain_type == 0 && topo < 2) ? 1.7 : 2.0;
-    b->chunk_div_short = true;
-    if (opt.chunk_div > 1.f) { b->chunk_div = opt.chunk_div; b->chunk_div_short = false; }
-    if (opt.min_chunk_steps > 0) b->min_chunk_steps = opt.min_chunk_steps;
-    if (const char* e = dev_env("NMF_SCHED")) b->chunking = std::string(e) != "plain";
-    if (const char* e = dev_env("NMF_ORDER")) {
-      const std::string v(e);
-      b->order_policy = v == "inorder" ? 0 : v == "costliest" ? 1 : v == "none" ? 2 : v == "policy" ? -1 : 3;
-    }
-    if (const char* e = dev_env("NMF_ORDER_EVERY")) b->order_every = std::max(1, atoi(e));
-    if (const char* e = dev_env("NMF_MAX_CHUNKS")) b->max_chunks = std::max(1, std::min(16, atoi(e)));
-    if (const char* e = dev_env("NMF_CHUNK_DIV")) { b->chunk_div = std::max(1.0, atof(e)); b->chunk_div_short = false; }
-    if (const char* e = dev_env("NMF_MIN_CHUNK_STEPS")) b->min_chunk_steps = std::max(1, atoi(e));
-    // (activations live in HBM and are advanced in place every step by the lane that owns the actuator: a world's steps must stay
-    // on one workgroup within a launch — whole-launch work items for the models that have general actuators)
-    if (d.act_general) b->chunking = false;
-    p = nullptr;
-    if (hipMalloc(&p, sizeof(nmf::SchedState)) == hipSuccess) {
-      (void)hipMemset(p, 0, sizeof(nmf::SchedState));
-      b->allocs.push_back(p); b->sched_buf = (nmf::SchedState*)p;
-    } else rc |= fail("nmf_batch_create: out of device memory");
-    st.sched = nullptr;
-    st.order = nullptr;
-    hipDeviceProp_t prop;
-    // flies (= single-wave workgroups) a CU holds at once: asked of the runtime for the kernel this batch will launch
-    // (LDS- or register-limited, whichever binds); fallback = the LDS-limited figures of the shipped build
-    int per_cu = topo < 2 ? 8 : (topo == 2 ? 4 : (topo == 3 ? 3 : (topo == 4 ? 8 : 5)));
-    {
-      const bool weld = b->dm.weld_active != 0, terrain = b->dm.terrain_type != 0;
-      if (weld && terrain) { nmf_batch_destroy(b); fail("nmf_batch_create: a tethered world has no terrain"); return nullptr; }
-      const void* fn = nullptr;
-#define NMF_FN(K, TOPO) if (topo == K) fn = weld ? reinterpret_cast<const void*>(&nmf::nmf_step_kernel<TOPO, true>) : terrain ? reinterpret_cast<const void*>(&nmf::nmf_step_kernel<nmf::Terrain<TOPO>, false>) : reinterpret_cast<const void*>(&nmf::nmf_step_kernel<TOPO, false>);
-#if NMF_HAS_TOPO(0)
-      NMF_FN(0, nmf::FlyTopo)
-#endif
-#if NMF_HAS_TOPO(1)
-      NMF_FN(1, nmf::FlyTopoActive)
-#endif
-#if NMF_HAS_TOPO(2)
-      NMF_FN(2, nmf::TreeTopoSmall)
-#endif
-#if NMF_HAS_TOPO(3)
-      NMF_FN(3, nmf::TreeTopo)
-#endif
-#if NMF_HAS_TOPO(4)
-      NMF_FN(4, nmf::FlyTopoBio)
-#endif
-#if NMF_HAS_TOPO(5)
-      NMF_FN(5, nmf::FlyTopoAll)
-#endif
-      if (!fn) { nmf_batch_destroy(b); fail("nmf_batch_create: this build of the library has no kernel for the model's skeleton (NMF_TOPO_MASK)"); return nullptr; }
-#undef NMF_FN
-      int nblk = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, fn, nmf::kWave, 0) == hipSuccess && nblk > 0) per_cu = nblk;
-      b->step_fn = fn;
-      // options.flies_per_cu below the kernel's own residency: idle LDS per workgroup so that k workgroups fit a CU and k + 1 do
-      // not — as little of it as that takes (allocation granule 512 B), so the CU keeps LDS for another stream's kernel
-      int want = opt.flies_per_cu;
-      if (const char* e = dev_env("NMF_FLIES_PER_CU")) want = atoi(e);
-      hipFuncAttributes fa;
-      if (want > 0 && want < per_cu && hipFuncGetAttributes(&fa, fn) == hipSuccess) {
-        int lds_cu = 0;
-        if (hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, device) != hipSuccess || lds_cu <= 0) lds_cu = 160 * 1024;
-        const int granule = 512;
-        int per_wg = (lds_cu / (want + 1) / granule + 1) * granule;            // the smallest allocation of which want + 1 do not fit
-        if (per_wg * want <= lds_cu && per_wg > (int)fa.sharedSizeBytes) {
-          b->lds_pad = (unsigned)(per_wg - (int)fa.sharedSizeBytes);
-          int nblk2 = 0;
-          if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk2, fn, nmf::kWave, b->lds_pad) == hipSuccess && nblk2 > 0) per_cu = std::min(per_cu, nblk2);
-          else per_cu = want;
-        }
-      }
-      if (const char* e = dev_env("NMF_LDS_PAD")) b->lds_pad = (unsigned)atoi(e);
-      b->per_cu = per_cu;
-    }
-    b->resident_waves = (hipGetDeviceProperties(&prop, device) == hipSuccess ? prop.multiProcessorCount : 256) * per_cu;
   }
-  if (rc != 0 || nmf_reset(b, nullptr) != 0 || hipDeviceSynchronize() != hipSuccess) {
-    std::string keep = g_err.empty() ? std::string("nmf_batch_create: device initialisation failed") : g_err;
+  if (const char* e = dev_env("NMF_LDS_PAD")) b->lds_pad = (unsigned)atoi(e);
+  b->per_cu = per_cu;
+  hipDeviceProp_t prop;
+  b->resident_waves = (hipGetDeviceProperties(&prop, device) == hipSuccess ? prop.multiProcessorCount : 256) * per_cu;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" nmf_batch* nmf_batch_create(const nmf_model* model, int n_worlds, int device) {
+  return nmf_batch_create_ex(model, n_worlds, device, nullptr);
+}
+
+extern "C" nmf_batch* nmf_batch_create_ex(const nmf_model* model, int n_worlds, int device, const nmf_batch_options* options) {
+  g_err.clear();
+  nmf_batch_options in{};
+  if (options) {
+    if (options->struct_size < (int32_t)sizeof(int32_t) || options->struct_size > (int32_t)sizeof(nmf_batch_options)) { fail("nmf_batch_create_ex: options->struct_size does not match this library"); return nullptr; }
+    memcpy(&in, options, (size_t)options->struct_size);
+  }
+  if (!model) { fail("nmf_batch_create: null model"); return nullptr; }
+  if (n_worlds <= 0) { fail("nmf_batch_create: n_worlds must be positive"); return nullptr; }
+  Skeleton sk;
+  if (classify_skeleton(model, sk) != 0) return nullptr;
+  DeviceGuard guard(device);            // allocations and the first reset run on `device`; the caller's device comes back on return
+  if (guard.err != hipSuccess) { fail("nmf_batch_create: hipSetDevice failed (no MI355X visible?)"); return nullptr; }
+  const Options opt = read_options(in);
+  auto* b = new nmf_batch();
+  b->model = model; b->n_worlds = n_worlds; b->device = device; b->topo = sk.topo;
+  if (fill_model(b, sk, opt) != 0 || alloc_state(b) != 0 || (set_schedule(b, opt), pick_kernel(b, opt)) != 0 ||
+      nmf_reset(b, nullptr) != 0 || hipDeviceSynchronize() != hipSuccess) {
+    const std::string keep = g_err.empty() ? std::string("nmf_batch_create: device initialisation failed") : g_err;
     nmf_batch_destroy(b);
     g_err = keep;
     return nullptr;
@@ -717,25 +720,10 @@ extern "C" int nmf_batch_info(const nmf_batch* b, int32_t out[16]) {
   if (!b || !out) return fail("nmf_batch_info: null argument");
   const bool weld = b->dm.weld_active != 0, terrain = b->dm.terrain_type != 0;
   int flavour = 0, maxcon = 0;
-  auto dual_of = [&](auto topo_tag) {
-    using TP = typename decltype(topo_tag)::type;
+  with_topo(b->topo, [&](auto tag) {      // the general-tree families have neither flavour (kDualS, kDualH false)
+    using TP = typename decltype(tag)::type;
     if (!weld && !(b->dm.solver_flags & 1)) { flavour = nmf::kDualS<TP> ? 1 : nmf::kDualH<TP> ? 2 : 0; maxcon = flavour ? nmf::kDualMaxCon<TP> : 0; }
-  };
-  switch (b->topo) {
-#if NMF_HAS_TOPO(0)
-    case 0: dual_of(TopoTag<nmf::FlyTopo>{}); break;
-#endif
-#if NMF_HAS_TOPO(1)
-    case 1: dual_of(TopoTag<nmf::FlyTopoActive>{}); break;
-#endif
-#if NMF_HAS_TOPO(4)
-    case 4: dual_of(TopoTag<nmf::FlyTopoBio>{}); break;
-#endif
-#if NMF_HAS_TOPO(5)
-    case 5: dual_of(TopoTag<nmf::FlyTopoAll>{}); break;
-#endif
-    default: break;
-  }
+  });
   out[0] = b->topo; out[1] = terrain ? 1 : 0; out[2] = weld ? 1 : 0; out[3] = flavour; out[4] = maxcon;
   out[5] = b->per_cu; out[6] = b->resident_waves; out[7] = b->chunking ? 1 : 0; out[8] = b->max_chunks;
   out[9] = (int32_t)std::lround(1000.0 * b->chunk_div); out[10] = b->order_policy; out[11] = b->dm.solver_flags;

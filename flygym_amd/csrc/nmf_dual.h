@@ -36,8 +36,7 @@
 // Code size matters here as much as instruction count: the step kernel's hot path fills the 64 KB instruction cache a pair
 // of CUs shares, so what runs once per row is a loop, and the elimination — unrolled by pivot ordinal, its multipliers live in
 // registers — is ordered so that only the blocks a step needs are ever fetched.
-// Development switches: NMF_DUAL_DEBUG (per-iteration printf of world 0), NMF_DUAL_NOWARM (no warm-start term),
-// NMF_DUAL_EXIT_FROM=<n> (first elimination at which the cost-based guards apply), NMF_NO_DUAL / NMF_NO_DUAL_HYBRID.
+// Development switch: NMF_DUAL_DEBUG (per-iteration printf of world 0).
 #pragma once
 
 namespace nmf {
@@ -221,14 +220,10 @@ __device__ __forceinline__ int dual_solve(FlyLds<TP>& s, const GModel& m, int la
   lane = opaque(lane);
   ncon = __builtin_amdgcn_readfirstlane(ncon);
   walls = __builtin_amdgcn_readfirstlane((int)walls) != 0;
-#ifdef NMF_DUAL_NOWARM
-  constexpr bool kWarm = false;
-#else
   // warm-start term c e (see kDualS / kDualH).  (Round 5 measured it on the hybrid kernels too, with the leg factors in HBM and
   // vA free for e: ALL_BIOLOGICAL 2.27 -> 1.92 eliminations per step but 8 bytes over its LDS budget, seven flies per CU, 30.7 ->
   // 26.2 M; ALL_POSSIBLE 2.14 -> 1.85 eliminations, 19.1 -> 18.5 M: e's twists and e.M.e over 210 dofs cost more than they save.)
   constexpr bool kWarm = kDualS<TP>;
-#endif
   const Frame fr0 = ld_frame(s, m);
   float (*const DFleg)[8] = dual_leg(s);
   float (*const DFroot)[8] = dual_root(s);
@@ -550,10 +545,7 @@ __device__ __forceinline__ int dual_solve(FlyLds<TP>& s, const GModel& m, int la
     // that are still moving.  A step the line search cuts short at a row's sign change improves the cost by next to nothing —
     // in float32 by less than the cost's rounding — yet the very next elimination, with that row's new state, may go all the
     // way (round 4: the worst one-step errors, up to 4e-2 of max |qacc| under 20x adhesion, were such exits).
-#ifndef NMF_DUAL_EXIT_FROM
-#define NMF_DUAL_EXIT_FROM 5
-#endif
-    if (!was_guess && iter >= NMF_DUAL_EXIT_FROM &&
+    if (!was_guess && iter >= kDualExitFrom &&
         (scale * improvement < m.tolerance || improvement <= kNoiseFactor * 1.1920929e-07f * fabsf(gauss + ccost))) { exit_bit = kExitCost; break; }
     mask = __ballot(on && jar < 0.f);
   }
@@ -567,13 +559,11 @@ __device__ __forceinline__ int dual_solve(FlyLds<TP>& s, const GModel& m, int la
   report = kExitDual | exit_bit | (npiv > kDualRegPivots ? kExitBigPivots : 0u) | ((unsigned int)npiv << 20);
   // An end that is not the exact one and whose last target violates more than kDualResidMax of the residuals is not taken: the
   // step goes to the primal loop (physics_forward).
-#ifndef NMF_NO_FALLBACK
   if (resid > kDualResidMax && !(m.solver_flags & 4)) {
     dual_restore(s, m, lane);
     report = kExitFallback | (report & kExitBigPivots) | ((unsigned int)npiv << 20);
     return -1;
   }
-#endif
   // the rows' forces
   float frow = on && jar < 0.f ? -D * jar : 0.f;
   // CPU flavour: the main solver's end point (multipliers and the warm-start scalar) — the next step's warm start is expanded

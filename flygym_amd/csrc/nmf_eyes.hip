@@ -117,9 +117,7 @@ __device__ __forceinline__ void lens_poly(float x, float& sc, float& cs) {
 // Waves per SIMD the register allocation aims at (measured per 8192 views with the own body: 5 waves 2.88 ms, 6 waves
 // 2.71, 7 waves 2.55 — with 24 spilled registers, still the fastest —, 8 waves 3.00): latency hiding beats the spills until
 // the allocation drops to 64 registers.
-#ifndef NMF_EYE_WAVES
-#define NMF_EYE_WAVES 7
-#endif
+constexpr int kEyeWaves = 7;
 // SAMPLED: the sampled mode (nmf_eye_params::rays_per_ommatidium = 16) as an instantiation of its own — the pixel-exact kernel
 // keeps its register allocation, this one has few live values and takes eight waves per SIMD.
 // RELIEF: the world has a terrain (flygym_amd/compose/world.py kinds 1-3) — the cell-by-cell walk of a ray through it exists in
@@ -127,7 +125,7 @@ __device__ __forceinline__ void lens_poly(float x, float& sc, float& cs) {
 // FRAMES: the call also wants the raw frames (inspection, parity tests); the readings-only instantiations carry neither the frame
 // bytes' registers nor their code through the pixel loop.
 template <bool SAMPLED, bool RELIEF, bool FRAMES>
-__global__ void __launch_bounds__(kEyeThreads) __attribute__((amdgpu_waves_per_eu(SAMPLED ? 8 : NMF_EYE_WAVES, SAMPLED ? 8 : NMF_EYE_WAVES)))
+__global__ void __launch_bounds__(kEyeThreads) __attribute__((amdgpu_waves_per_eu(SAMPLED ? 8 : kEyeWaves, SAMPLED ? 8 : kEyeWaves)))
 nmf_eye_kernel(EyeArgs A, const float* __restrict__ seg_xpos, const float* __restrict__ seg_xquat, int nseg,
                const float* __restrict__ spheres, const int* __restrict__ cap_seg, const float* __restrict__ cap_geom,
                const u32x4* __restrict__ plan, const int* __restrict__ visit, const float* __restrict__ cones, const float4* __restrict__ chunk_cones, int n_groups,

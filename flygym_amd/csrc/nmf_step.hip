@@ -24,13 +24,9 @@ namespace nmf {
 
 // Stage boundaries.  One wave per workgroup, and the LDS unit takes a wave's operations in order: a read that follows
 // another lane's write in program order sees it, so a boundary only has to order the accesses for the COMPILER — a
-// wavefront-scope fence.  __syncthreads() (NMF_WSYNC_BARRIER, the round-1/2 behaviour) additionally parks the wave on
-// `s_waitcnt lgkmcnt(0)` until its LDS writes have drained: ~60 times per step, 1.2 % of the launch.
-#ifdef NMF_WSYNC_BARRIER
-#define WSYNC() __syncthreads()
-#else
+// wavefront-scope fence.  __syncthreads() (the round-1/2 behaviour) additionally parks the wave on `s_waitcnt lgkmcnt(0)`
+// until its LDS writes have drained: ~60 times per step, 1.2 % of the launch.
 #define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
-#endif
 // NMF_TOPO_MASK (development builds only: `scripts/build_variant.sh x -DNMF_TOPO_MASK=1` compiles the LEGS_ONLY kernels alone,
 // in a sixth of the time): bit k keeps the kernels of topology k (0 LEGS_ONLY, 1 LEGS_ACTIVE_ONLY, 2 / 3 general tree,
 // 4 ALL_BIOLOGICAL, 5 ALL_POSSIBLE).  The shipped library has all of them.
@@ -60,6 +56,7 @@ constexpr int kDualRegPivots = 47;
 // contact-space solves that do not end exactly: what the last target may violate, relative to the largest residual, before the step is
 // solved again on the primal loop (the tie rule's own bound)
 constexpr float kDualResidMax = 1e-3f;
+constexpr int kDualExitFrom = 5;     // first elimination at which the contact-space solve's cost-based guards apply (nmf_dual.h)
 
 // Optional per-stage cycle accounting (s_memtime deltas of wave 0 / lane 0), built only with
 // -DNMF_STAGE_PROFILE into a separate diagnostic library; the product build has no trace of it.
@@ -151,11 +148,7 @@ struct TreeLds<TP, true, true> {   // hybrid kernels: the same for the rest bodi
 // pyramid-coefficient matrix of every contact (c_m3) and every body's inertia as a symmetric 6x6 (Isym: six reads with
 // lane-constant offsets that the compiler pairs into ds_read2); the hybrid kernels (LDS-bound) rebuild the former from
 // the active-row mask and read inertia rows through InertiaRowMap
-#ifdef NMF_LDS_DIET     // experiment: every kernel on the LDS-bound layout (three waves per SIMD need <= 13.6 KB per fly)
-template <class TP> constexpr bool has_cm3() { return false; }
-#else
 template <class TP> constexpr bool has_cm3() { if constexpr (TP::kStar) return TP::REST_B == 0; else return false; }
-#endif
 template <class TP> inline constexpr bool kHasCm3 = has_cm3<TP>();
 template <class TP> inline constexpr bool kHasIsym = has_cm3<TP>();
 
@@ -195,7 +188,6 @@ template <class TP> constexpr int row_width_tw() { if constexpr (TP::kStar) retu
 // One kernel per skeleton and world kind whatever the batch size: a world's result does not depend on how many worlds step
 // beside it (rounds 3-4 had a second LEGS_ONLY flavour for small batches, nmf::Wide, because A's row triangle for 16 contacts
 // cost two flies per CU).
-// NMF_NO_DUAL: development switch, every step on the primal loop.
 template <class TP> constexpr bool dual_hybrid() {
   if constexpr (TP::kStar) return TP::REST_B > 0; else return false;
 }
@@ -205,17 +197,8 @@ template <class TP> constexpr bool dual_hybrid() {
 template <class TP> constexpr bool dual_global() {
   if constexpr (TP::kStar) return TP::REST_B > 0 && 4 * TP::NV < TP::NLEG * TP::NDL * 8; else return false;
 }
-#ifdef NMF_NO_DUAL
-template <class TP> inline constexpr bool kDualS = false;
-template <class TP> inline constexpr bool kDualH = false;
-#else
 template <class TP> inline constexpr bool kDualS = has_cm3<TP>();
-#ifdef NMF_NO_DUAL_HYBRID
-template <class TP> inline constexpr bool kDualH = false;
-#else
 template <class TP> inline constexpr bool kDualH = dual_hybrid<TP>();
-#endif
-#endif
 template <class TP> inline constexpr bool kDual = kDualS<TP> || kDualH<TP>;
 template <class TP> inline constexpr bool kDualGlob = kDualH<TP> && dual_global<TP>();
 constexpr int kDualScratchFloats = 8 * 6 * 24;      // per workgroup: the leg factors of the largest skeleton (six legs of 24 hinges)
@@ -544,7 +527,6 @@ __device__ __noinline__ void stage_kinematics(FlyLds<TP>& s, const GModel& m, in
     float R0 = s.xmat()[0][3 * r3], R1 = s.xmat()[0][3 * r3 + 1], R2 = s.xmat()[0][3 * r3 + 2];
     float p = s.xpos()[0][r3];
     const int b0 = TP::LB0 + L.lg * TP::NBL;
-#ifndef NMF_KIN_NO_PREFETCH
     // the relative transform of level l + 1 is requested before level l's results are stored: its LDS round trip runs
     // under the stores (the compiler keeps the loads behind them otherwise — it cannot tell the two regions apart)
     float Mn[12];
@@ -568,19 +550,6 @@ __device__ __noinline__ void stage_kinematics(FlyLds<TP>& s, const GModel& m, in
       s.xmat()[b0 + l][3 * r3] = R0; s.xmat()[b0 + l][3 * r3 + 1] = R1; s.xmat()[b0 + l][3 * r3 + 2] = R2;
       s.xpos()[b0 + l][r3] = p;
     });
-#else
-    static_for<TP::NBL>([&](auto I) {
-      constexpr int l = decltype(I)::value;
-      const float* M = relm[b0 + l];
-      p += R0 * M[9] + R1 * M[10] + R2 * M[11];
-      const float n0 = R0 * M[0] + R1 * M[3] + R2 * M[6];
-      const float n1 = R0 * M[1] + R1 * M[4] + R2 * M[7];
-      const float n2 = R0 * M[2] + R1 * M[5] + R2 * M[8];
-      R0 = n0; R1 = n1; R2 = n2;
-      s.xmat()[b0 + l][3 * r3] = R0; s.xmat()[b0 + l][3 * r3 + 1] = R1; s.xmat()[b0 + l][3 * r3 + 2] = R2;
-      s.xpos()[b0 + l][r3] = p;
-    });
-#endif
   }
   WSYNC();
   for (int j = lane; j < s.nv(); j += kWave) {
@@ -2881,16 +2850,10 @@ __device__ void write_poses(FlyLds<TP>& s, const GModel& m, const DevState& st, 
 }
 
 // Waves per SIMD the register allocation aims at: two (256 VGPRs).  Three (168 VGPRs) were measured on both leg-chain
-// skeletons (-DNMF_WAVES_PER_EU=3): the 72-dof kernel gains nothing (the LDS array saturates), the
+// skeletons: the 72-dof kernel gains nothing (the LDS array saturates), the
 // 48-dof one +18 % with 70 spilled registers in an early round-2 build but -12 % with the 116 the persistent item loop
 // leaves it — not shipped.
-template <class TP> constexpr int waves_per_simd() {
-#ifdef NMF_WAVES_PER_EU
-  return NMF_WAVES_PER_EU;
-#else
-  return 2;
-#endif
-}
+template <class TP> constexpr int waves_per_simd() { return 2; }
 
 // What every kernel of a batch stages in LDS once per launch: the tree tables (kernels with tree sweeps), the per-dof
 // diagonal terms, the per-row constants of the contact stiffness rows / inertia rows, and — star kernels with LDS to spare —
@@ -3096,12 +3059,10 @@ __global__ void __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(wave
         const unsigned int rep = (unsigned int)__builtin_amdgcn_readfirstlane(s.iters);
         sum_con += (unsigned int)s.ncon; sum_it += rep & 0xffu; sum_of += (unsigned int)s.overflow;
         sum_dual += (rep >> 8) & 1u; sum_kkt += (rep >> 9) & 1u;
-#ifndef NMF_NO_EXIT_COUNT
         if (rep & (0xffcu << 8)) {
           const int xl = opaque(lane) - 6;
           if (xl >= 2 && xl < kExitKinds && ((rep >> (8 + xl)) & 1u)) add_count(&st.stats_sum[16 * (size_t)w + 4 + xl], 1u);
         }
-#endif
       }
     }
     TRACE_BUSY_END();

@@ -182,6 +182,52 @@ def test_batch_info_names_what_runs(torch_mod, monkeypatch):
     assert info["kernel_family"] == 4 and info["contact_space_flavour"] == 2 and info["contact_space_max_contacts"] == 13 and info["flies_per_cu"] == 8
 
 
+_ENV_CHILD = """
+import json, sys
+import numpy as np
+import torch
+from flygym_amd import HIPSimulation, make_model
+
+opts = dict(solver="primal", sched="plain", order="inorder", max_chunks=5, min_chunk_steps=3, order_every=2, chunk_div=3.0, flies_per_cu=6)
+legs = HIPSimulation(make_model()[1], n_worlds=8, device=0, _options=opts).batch_info()
+bio = HIPSimulation(make_model(joints_preset="all_biological")[1], n_worlds=4, device=0)
+bio.step(60)
+torch.cuda.synchronize()
+print(json.dumps(dict(legs=legs, bio=bio.batch_info(), bio_qpos=bio.field("qpos").cpu().numpy().tobytes().hex())))
+"""
+
+
+def test_dev_env_overrides_beat_the_options(torch_mod):
+    """Under ``NMF_ALLOW_ENV=1`` the library's development overrides (``scripts/gpu_ab.py`` sweeps ``bench.py`` through them)
+    beat the create options, with their own clamping: ``NMF_MAX_CHUNKS=0`` is one chunk, ``NMF_CHUNK_DIV`` keeps its double
+    precision (1.0005: 1001 in thousandths, a float would give 1000), ``NMF_SCHED=chunks`` turns chunking back on over
+    ``sched="plain"``, ``NMF_DISABLE_REST_FAST`` is the ``rest_slow`` option (bit-identical states).  A fresh child process:
+    the library reads the gate once per process."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from flygym_amd import HIPSimulation, make_model
+
+    root = Path(__file__).resolve().parents[1]
+    env = dict(os.environ, NMF_ALLOW_ENV="1", NMF_SOLVER="nohist", NMF_SCHED="chunks", NMF_ORDER="costliest", NMF_MAX_CHUNKS="0",
+               NMF_CHUNK_DIV="1.0005", NMF_MIN_CHUNK_STEPS="0", NMF_ORDER_EVERY="-3", NMF_FLIES_PER_CU="4", NMF_DISABLE_REST_FAST="1")
+    r = subprocess.run([sys.executable, "-c", _ENV_CHILD], capture_output=True, text=True, env=env, cwd=root, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    legs, bio = out["legs"], out["bio"]
+    assert legs["solver_option_bits"] == 2 and legs["contact_space_flavour"] == 1
+    assert legs["chunked"] == 1 and legs["order_policy"] == 1 and legs["max_chunks"] == 1 and legs["chunk_div_x1000"] == 1001
+    assert legs["flies_per_cu"] == 4 and legs["resident_workgroups"] == 4 * 256
+    assert bio["kernel_family"] == 4 and bio["solver_option_bits"] == 2 and bio["flies_per_cu"] == 4
+    # the same batch in this process (no gate) with the options the overrides stand for
+    sim = HIPSimulation(make_model(joints_preset="all_biological")[1], n_worlds=4, device=0,
+                        _options=dict(solver="nohist", rest_slow=True, flies_per_cu=4))
+    sim.step(60)
+    torch_mod.cuda.synchronize()
+    assert sim.field("qpos").cpu().numpy().tobytes().hex() == out["bio_qpos"]
+
+
 def test_round5_entry_points_refuse_bad_arguments(torch_mod):
     """The C ABI of the round-5 entry points fails loudly (non-zero return + ``nmf_last_error``) and leaves the batch as it
     was: zero or negative step counts, an observation interval of zero, a null ring, a ring row too short for the block it
