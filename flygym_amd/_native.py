@@ -58,7 +58,7 @@ INFO_KEYS = ("kernel_family", "terrain_kernel", "tether_kernel", "contact_space_
 
 def build(force: bool = False, verbose: bool = False) -> Path:
     """Compile the HIP engine for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [CSRC / "nmf_capi.hip", CSRC / "nmf_step.hip", CSRC / "nmf_sensors.hip", CSRC / "nmf_eyes.hip", CSRC / "nmf_replay.hip", CSRC / "nmf_device.h", CSRC / "nmf_tree.h", CSRC / "nmf_dual.h",
+    srcs = [CSRC / "nmf_capi.hip", CSRC / "nmf_step.hip", CSRC / "nmf_sensors.hip", CSRC / "nmf_eyes.hip", CSRC / "nmf_camera.hip", CSRC / "nmf_replay.hip", CSRC / "nmf_device.h", CSRC / "nmf_tree.h", CSRC / "nmf_dual.h",
             INCLUDE / "nmf.h", Path(__file__)]   # this file holds the compiler flags
     if os.environ.get("NMF_HIP_LIB"):
         return LIB_PATH                       # an externally built variant: nothing to compile here
@@ -149,6 +149,10 @@ def lib():
             "nmf_eye_plan_create": (vp, [vp, vp, vp, vp, ci, ci, cf, ci, ci]),
             "nmf_eye_plan_destroy": (None, [vp]),
             "nmf_eye_render_planned": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+            "nmf_camera_params_size": (ctypes.c_size_t, []),
+            "nmf_camera_plan_create": (vp, [vp, vp, ci, vp, ci, vp, vp, vp, ci]),
+            "nmf_camera_plan_destroy": (None, [vp]),
+            "nmf_camera_render": (ci, [vp, vp, vp, vp, vp]),
             "nmf_odor_intensity": (ci, [vp, vp, vp, ci, vp, vp, ci, ci, vp, vp]),
             "nmf_replay_resample": (ci, [vp, ci, ci, ctypes.c_double, ctypes.c_double, vp, ci, ci, vp, vp]),
         }

@@ -1,0 +1,304 @@
+// nmf_camera.hip — batch camera renderer for selected worlds of a batch (gfx950): the camera a person looks through.
+//
+// Replaces the reference's WarpGPUBatchRenderer (warp/rendering.py:279-341: mjw.refit_bvh + mjw.render + a gather of the selected
+// worlds and cameras, attached by warp/simulation.py:266-342).  Camera model, scene and shading are build-defined
+// and pinned by the numpy specification tests/camera_spec.py: pinhole cameras ("fixed" in the world, or "track": at the fly's
+// root segment + a constant offset, orientation constant in the world), the eyes' scene (checker ground or the terrain relief of
+// the physics, sky, up to 8 spheres) plus the WHOLE fly as capsules, each with its own colour, lit by one directional light from
+// straight above: colour = base * (ambient + diffuse * max(0, n_z)).
+//
+// Grid: (32 x 32-pixel image tile, camera, selected world) — the world comes from a device list, so 4 of 4096 worlds cost 4
+// worlds.  Per workgroup, once: the camera pose and the capsules' world-space end points relative to the camera, in LDS.  A
+// wave takes 8 x 8-pixel patches of the tile, one pixel per lane: it culls once per patch, lane = object, against the patch's
+// bounding cone (two rounds: capsules 0..63, then capsules 64..71 and the spheres) and decides whether any ray of the patch
+// points below the horizon, exactly as the eye kernel does per group; then every lane intersects the survivors only (loops over
+// wave-uniform bit masks: scalar control flow), keeps the nearest hit with the z component of its normal, shades and converts.
+// The tile is staged in LDS and leaves as dwords of whole row segments.
+//
+// The terrain cell arithmetic (terrain_cell, floor_int, kTerrainEps, kTerrainWallTol, kMaxTerrainCells) is nmf_eyes.hip's own:
+// this file is compiled after it in the library's translation unit and calls those functions as they are.  The relief walk, the
+// ray-capsule and the ray-sphere arithmetic are written out again here instead of being moved into a shared header: they carry the
+// hit's normal with them, which the eyes do not need, take their discriminants in a better-conditioned form (see `ball` below: the
+// shade of a grazing hit needs it, a material id does not), and the eye frames are pinned pixel for pixel — nmf_eyes.hip stays
+// untouched, and the two copies are not merged into a header.
+#include "nmf_device.h"
+
+#pragma clang fp reassociate(off)
+
+namespace nmf {
+
+constexpr int kCamThreads = 256;
+constexpr int kCamTile = 32;             // a workgroup's tile: 32 x 32 pixels, sixteen 8 x 8 patches, four per wave
+constexpr int kCamMaxCaps = 72;          // the engine's segment limit (the eyes see at most 64 of them)
+
+struct CamView {
+  int mode, seg;            // 0 fixed: pos is a world position; 1 track: pos is added to the position of segment `seg`
+  float pos[3];
+  float rot[9];             // camera axes in the world (columns: right, up, back), row-major
+  float tan_px;             // tan(fovy / 2) / (H / 2): camera-frame extent of a pixel at unit depth
+};
+
+struct CamArgs {
+  int height, width, tiles_x;
+  float ambient, diffuse;
+  float checker_size, ground_z;
+  int n_spheres, sphere_stride;
+  int terrain_kind;
+  float terrain[5];
+  int n_caps;
+  unsigned char rgb[4 + kMaxSpheres][4];    // 0 sky, 1 ground A, 2 ground B, 3 terrain side wall, 4.. spheres
+};
+
+__global__ void __launch_bounds__(kCamThreads)
+nmf_camera_kernel(CamArgs A, const CamView* __restrict__ views, const int* __restrict__ world_ids,
+                  const float* __restrict__ seg_xpos, const float* __restrict__ seg_xquat, int nseg,
+                  const float* __restrict__ spheres, const int* __restrict__ cap_seg, const float* __restrict__ cap_geom,
+                  const unsigned int* __restrict__ cap_rgb, uint8_t* __restrict__ frames_out) {
+  // capsules relative to the camera, world axes: 0-2 pa, 3-5 unit axis n, 6 length, 7 -pa.n, 8-10 the part of -pa across the axis,
+  // 11 r^2, 12 1 / r, 13-15 pb, 16 the colour word
+  __shared__ float capd[kCamMaxCaps][20];
+  __shared__ float capc[kCamMaxCaps][3][5];      // angular cover: three discs (unit direction, cos / sin of the angular radius)
+  __shared__ float sph[kMaxSpheres][8];          // centre - camera, r^2, 1 / r, the colour word
+  __shared__ float sphc[kMaxSpheres][5];
+  __shared__ float camp[3];
+  __shared__ unsigned int tile[kCamTile * kCamTile * 3 / 4];
+
+  const int cam_i = blockIdx.y, sel = blockIdx.z;
+  const int w = world_ids[sel];
+  const CamView& V = views[cam_i];
+  if (threadIdx.x < 3) {
+    float p = V.pos[threadIdx.x];
+    if (V.mode == 1) p += seg_xpos[((size_t)w * nseg + V.seg) * 3 + threadIdx.x];
+    camp[threadIdx.x] = p;
+  }
+  __syncthreads();
+  auto uni = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
+  const V3 cam = v3(uni(camp[0]), uni(camp[1]), uni(camp[2]));
+  float R[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) R[i] = uni(V.rot[i]);
+  const float tpx = uni(V.tan_px);
+  if (threadIdx.x < A.n_spheres) {
+    const int s = threadIdx.x;
+    const float* g = spheres + (size_t)w * A.sphere_stride + 4 * s;
+    const float r = g[3];
+    const V3 oc = cam - v3(g[0], g[1], g[2]);
+    float* q = sph[s];
+    q[0] = -oc.x; q[1] = -oc.y; q[2] = -oc.z; q[3] = r * r; q[4] = 1.0f / r;      // centre - camera
+    unsigned int word; __builtin_memcpy(&word, A.rgb[4 + s], 4);
+    q[5] = __builtin_bit_cast(float, word);
+    const float dist = sqrtf(dot(oc, oc));
+    const float inv = dist > 1e-6f ? 1.0f / dist : 0.f;
+    float* c = sphc[s];
+    c[0] = -oc.x * inv; c[1] = -oc.y * inv; c[2] = -oc.z * inv;
+    const float ang = dist > r ? asinf(r / dist) + 0.03f : 3.2f;
+    c[3] = ang < 3.1f ? cosf(ang) : -2.f; c[4] = ang < 3.1f ? sinf(ang) : 0.f;
+  }
+  if (threadIdx.x >= 64 && threadIdx.x - 64 < A.n_caps) {      // (waves 1 and 2: the spheres are wave 0's)
+    const int c = threadIdx.x - 64, cs = cap_seg[c];
+    const float* g = cap_geom + 7 * c;
+    float Rc[9];
+    qmat(Rc, ldq(seg_xquat + ((size_t)w * nseg + cs) * 4));
+    const V3 xp = ld3(seg_xpos + ((size_t)w * nseg + cs) * 3);
+    const V3 pa = (xp + mat_vec(Rc, ld3(g))) - cam, pb = (xp + mat_vec(Rc, ld3(g + 3))) - cam;
+    const float r = g[6];
+    const V3 ba = pb - pa;
+    const float baba = dot(ba, ba);
+    const float len = sqrtf(baba), ilen = len > 1e-9f ? 1.0f / len : 0.f;
+    const V3 nx = ilen * ba;
+    const float on = -dot(pa, nx);
+    float* q = capd[c];
+    q[0] = pa.x; q[1] = pa.y; q[2] = pa.z; q[3] = nx.x; q[4] = nx.y; q[5] = nx.z; q[6] = len; q[7] = on;
+    q[8] = -pa.x - on * nx.x; q[9] = -pa.y - on * nx.y; q[10] = -pa.z - on * nx.z;
+    q[11] = r * r; q[12] = 1.0f / r; q[13] = pb.x; q[14] = pb.y; q[15] = pb.z;
+    q[16] = __builtin_bit_cast(float, cap_rgb[c]); q[17] = 0.f; q[18] = 0.f; q[19] = 0.f;
+    // angular cover as in the eye kernel: the thirds of the axis, each inside a sphere of radius (length / 6 + r)
+    const float Rb = sqrtf(baba) * (1.0f / 6.0f) + r;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const V3 mid = pa + ((2.f * (float)i + 1.f) * (1.0f / 6.0f)) * ba;
+      const float dist = sqrtf(dot(mid, mid));
+      const float inv = dist > 1e-6f ? 1.0f / dist : 0.f;
+      const float ang = dist > Rb ? asinf(Rb / dist) + 0.004f : 3.2f;       // camera inside the bound: always a candidate
+      float* cq = capc[c][i];
+      cq[0] = mid.x * inv; cq[1] = mid.y * inv; cq[2] = mid.z * inv;
+      cq[3] = ang < 3.1f ? cosf(ang) : -2.f; cq[4] = ang < 3.1f ? sinf(ang) : 0.f;
+    }
+  }
+  __syncthreads();
+
+  auto rgb_word = [&](int mtl) { unsigned int v; __builtin_memcpy(&v, A.rgb[mtl], 4); return v; };      // (kernel argument: scalar loads)
+  const unsigned int w_sky = rgb_word(0), w_ga = rgb_word(1), w_gb = rgb_word(2), w_wall = rgb_word(3), w_gx = w_ga ^ w_gb;
+  const float inv_cs = 1.0f / A.checker_size;
+  const float hz = cam.z - A.ground_z;
+  const float cx = 0.5f * (float)A.width, cy = 0.5f * (float)A.height;
+  const int tile_y = blockIdx.x / A.tiles_x, tile_x = blockIdx.x - tile_y * A.tiles_x;
+  const int row0 = tile_y * kCamTile, col0 = tile_x * kCamTile;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lx = lane & 7, ly = lane >> 3;
+  uint8_t* const tile_b = reinterpret_cast<uint8_t*>(tile);
+
+  auto to_world = [&](float x, float y, float z) { return v3(R[0] * x + R[1] * y + R[2] * z, R[3] * x + R[4] * y + R[5] * z, R[6] * x + R[7] * y + R[8] * z); };
+  // does a cone (axis a, half-angle by cos / sin) meet a disc of angular radius (qc, qs) about the unit direction q?  (nmf_eyes.hip)
+  auto meets = [](V3 a, float c_cos, float c_sin, const float* q) {
+    const float ca = q[0] * a.x + q[1] * a.y + q[2] * a.z;
+    return (int)(q[3] < -1.5f) | (int)(ca >= c_cos * q[3] - c_sin * q[4]) | (int)(c_sin * q[3] + c_cos * q[4] <= 0.f);
+  };
+
+#pragma unroll 1
+  for (int pass = 0; pass < 4; ++pass) {
+    // the wave's patch: 8 x 8 pixels at (row0 + 8 pass, col0 + 8 wave)
+    const int pr0 = row0 + 8 * pass, pc0 = col0 + 8 * wave;
+    if (pr0 >= A.height || pc0 >= A.width) continue;             // (wave-uniform) wholly outside the image
+    // bounding cone of the patch's rays, camera frame: the axis through its centre, the widest of its four corners
+    const float uc = ((float)(pc0 + 4) - cx) * tpx, vc = ((float)(pr0 + 4) - cy) * tpx;
+    const float ic = __builtin_amdgcn_rsqf(uc * uc + vc * vc + 1.f);
+    const V3 ax_c = v3(uc * ic, -vc * ic, -ic);
+    float g_cos = 1.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float u = ((float)(pc0 + 8 * (k & 1)) - cx) * tpx, v = ((float)(pr0 + 8 * (k >> 1)) - cy) * tpx;
+      const float in = __builtin_amdgcn_rsqf(u * u + v * v + 1.f);
+      g_cos = fminf(g_cos, (u * ax_c.x - v * ax_c.y - ax_c.z) * in);
+    }
+    g_cos = fmaxf(g_cos - 1e-5f, 0.f);       // (a patch of a pinhole image spans far less than a right angle)
+    const float g_sin = sqrtf(fmaxf(1.f - g_cos * g_cos, 0.f));
+    const V3 gw = to_world(ax_c.x, ax_c.y, ax_c.z);
+    // round 1: lane = capsule 0..63; round 2: lanes 0..7 = capsules 64..71, lanes 8..15 = the spheres
+    int sees = 0;
+    if (lane < A.n_caps) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) sees |= meets(gw, g_cos, g_sin, capc[lane][i]);
+    }
+    const unsigned long long caps_lo = __ballot(sees != 0);
+    sees = 0;
+    if (lane < 8 && 64 + lane < A.n_caps) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) sees |= meets(gw, g_cos, g_sin, capc[64 + lane][i]);
+    } else if (lane >= 8 && lane < 8 + A.n_spheres) {
+      sees = meets(gw, g_cos, g_sin, sphc[lane - 8]);
+    }
+    const unsigned int round2 = (unsigned int)__ballot(sees != 0);
+    const unsigned int caps_hi = round2 & 0xffu, grp_sph = (round2 >> 8) & 0xffu;
+    const bool grp_ground = gw.z < g_sin + 1e-3f;                // some ray of the patch points below the horizon
+
+    // this lane's pixel
+    const int row = pr0 + ly, col = pc0 + lx;
+    const float u = ((float)col + 0.5f - cx) * tpx, v = ((float)row + 0.5f - cy) * tpx;
+    const float inorm = __builtin_amdgcn_rsqf(u * u + v * v + 1.f);
+    const V3 d = to_world(u * inorm, -v * inorm, -inorm);
+
+    unsigned int rgb = w_sky;
+    float tbest = INFINITY, nz = 0.f;
+    bool lit = false;                      // the sky has no surface: its colour is not shaded
+    if (grp_ground) {
+      const float t = -hz * __builtin_amdgcn_rcpf(d.z);
+      const bool ghit = d.z < 0.f && t > 0.f;
+      const float gx = (cam.x + t * d.x) * inv_cs, gy = (cam.y + t * d.y) * inv_cs;
+      const unsigned int pm = (unsigned int)(((floor_int(gx) + floor_int(gy)) << 31) >> 31);
+      rgb = ghit ? (w_ga ^ (pm & w_gx)) : w_sky;
+      tbest = ghit ? t : INFINITY; nz = 1.f; lit = ghit;
+      if (A.terrain_kind != 0 && d.z < 0.f) {
+        // relief: follow the ray through the cells of h(x, y) from the highest level down (nmf_eyes.hip's walk; a top has
+        // n_z = 1, a side wall n_z = 0)
+        const float rdz = 1.0f / d.z;
+        float tc = fmaxf(0.f, (A.ground_z + A.terrain[4] - cam.z) * rdz);
+#pragma unroll 1
+        for (int it = 0; it < kMaxTerrainCells; ++it) {
+          const float tp = tc + kTerrainEps;
+          const TerrainCell c = terrain_cell(A.terrain_kind, A.terrain, cam.x + tp * d.x, cam.y + tp * d.y);
+          const float h = c.h + A.ground_z;
+          const float z_in = cam.z + tc * d.z;
+          if (z_in < h - kTerrainWallTol) { tbest = tc; rgb = w_wall; nz = 0.f; lit = true; break; }
+          const float tx = d.x > 0.f ? (c.x1 - cam.x) / d.x : (d.x < 0.f ? (c.x0 - cam.x) / d.x : INFINITY);
+          const float ty = d.y > 0.f ? (c.y1 - cam.y) / d.y : (d.y < 0.f ? (c.y0 - cam.y) / d.y : INFINITY);
+          const float t_out = fminf(tx, ty);
+          const float t_h = (h - cam.z) * rdz;
+          if (t_h <= t_out) {
+            const float qx = (cam.x + t_h * d.x) * inv_cs, qy = (cam.y + t_h * d.y) * inv_cs;
+            tbest = t_h; rgb = ((floor_int(qx) + floor_int(qy)) & 1) ? w_gb : w_ga; nz = 1.f; lit = true;
+            break;
+          }
+          tc = t_out;
+        }
+      }
+    }
+    // Discriminants in the well-conditioned form: a ray (unit d) passes a point c at the distance |d x c|, so it meets the sphere
+    // of radius r about c iff r^2 - |d x c|^2 >= 0 — a difference of two numbers of the size of r^2.  The textbook form
+    // (d.c)^2 - (c.c - r^2) subtracts numbers of the size of the DISTANCE squared: with a 0.1 mm leg segment 10 mm away float32
+    // loses four digits there, the root moves by micrometres along a grazing ray and the normal — hence the shade — by several
+    // grey levels at every silhouette.
+    auto ball = [&](float cx_, float cy_, float cz_, float r2, float& t) {       // nearest hit with the sphere about c; false: the ray misses it
+      const float kx = d.y * cz_ - d.z * cy_, ky = d.z * cx_ - d.x * cz_, kz = d.x * cy_ - d.y * cx_;
+      const float disc = r2 - (kx * kx + ky * ky + kz * kz);
+      t = (d.x * cx_ + d.y * cy_ + d.z * cz_) - __builtin_amdgcn_sqrtf(fmaxf(disc, 0.f));
+      return disc > 0.f && t > 0.f;
+    };
+    for (unsigned int sm = grp_sph; sm; sm &= sm - 1u) {
+      const int s = __ffs((int)sm) - 1;
+      const float* q = sph[s];
+      float ts;
+      const bool ok = ball(q[0], q[1], q[2], q[3], ts) && ts < tbest;
+      if (ok) { tbest = ts; rgb = __builtin_bit_cast(unsigned int, q[5]); nz = (ts * d.z - q[2]) * q[4]; lit = true; }
+    }
+    auto capsule = [&](int ci) {
+      const float* q = capd[ci];
+      // across the axis n: the ray's direction dp and the camera's offset op (from the capsule's data); the side is hit where
+      // the ray passes the axis at the distance r: a t^2 + 2 (dp.op) t + |op|^2 - r^2 = 0, discriminant a r^2 - |dp x op|^2
+      const float dn = q[3] * d.x + q[4] * d.y + q[5] * d.z;
+      const float px = d.x - dn * q[3], py = d.y - dn * q[4], pz = d.z - dn * q[5];
+      const float a = px * px + py * py + pz * pz;
+      const float kx = py * q[10] - pz * q[9], ky = pz * q[8] - px * q[10], kz = px * q[9] - py * q[8];
+      const float hq = a * q[11] - (kx * kx + ky * ky + kz * kz);
+      const float tb = (-(px * q[8] + py * q[9] + pz * q[10]) - __builtin_amdgcn_sqrtf(fmaxf(hq, 0.f))) / a;
+      const float yy = q[7] + tb * dn;             // along the axis, from pa
+      const bool cyl = hq >= 0.f && a > 1e-12f;
+      float tcap = INFINITY, zc = 0.f;        // zc: z of the axis point the hit's normal starts from (relative to the camera)
+      if (cyl && yy > 0.f && yy < q[6] && tb > 0.f) { tcap = tb; zc = q[2] + q[5] * yy; }
+      else {
+        const bool use_a = !(yy > 0.f) || !cyl;
+        float te;
+        const bool hit_end = ball(use_a ? q[0] : q[13], use_a ? q[1] : q[14], use_a ? q[2] : q[15], q[11], te);
+        if (hit_end) { tcap = te; zc = use_a ? q[2] : q[15]; }
+      }
+      if (tcap < tbest) { tbest = tcap; rgb = __builtin_bit_cast(unsigned int, q[16]); nz = (tcap * d.z - zc) * q[12]; lit = true; }
+    };
+    for (unsigned long long cm = caps_lo; cm; cm &= cm - 1ull) capsule(__ffsll((long long)cm) - 1);
+    for (unsigned int cm = caps_hi; cm; cm &= cm - 1u) capsule(64 + __ffs((int)cm) - 1);
+
+    // one light from straight above; rounded as vision._u8 rounds (floor(x + 0.5)), saturating
+    const float f = lit ? A.ambient + A.diffuse * fmaxf(nz, 0.f) : 1.f;
+    uint8_t* o = tile_b + ((8 * pass + ly) * kCamTile + 8 * wave + lx) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float x = (float)((rgb >> (8 * c)) & 0xffu) * f + 0.5f;
+      o[c] = (uint8_t)min(max(floor_int(x), 0), 255);
+    }
+  }
+  __syncthreads();
+
+  // the tile leaves as dwords of whole row segments: a row of the tile is [g0, g1) of the frame array's bytes; its aligned
+  // dwords are assembled from the staged bytes, the (at most 3 + 3) bytes before and after them — only where the row segment
+  // does not start or end on a dword: image widths that are no multiple of 4 — go out as bytes
+  const int wseg = min(kCamTile, A.width - col0), hseg = min(kCamTile, A.height - row0);
+  const size_t frame0 = ((size_t)sel * gridDim.y + cam_i) * (size_t)A.height * A.width * 3;
+  for (int i = threadIdx.x; i < hseg * 24; i += kCamThreads) {
+    const int r = i / 24, k = i - r * 24;
+    const size_t g0 = frame0 + ((size_t)(row0 + r) * A.width + col0) * 3, g1 = g0 + (size_t)wseg * 3;
+    const size_t a0 = (g0 + 3) & ~(size_t)3;
+    const size_t a = a0 + 4 * (size_t)k;
+    const uint8_t* src = tile_b + r * kCamTile * 3;
+    if (a + 4 <= g1) {
+      const int off = (int)(a - g0);
+      const unsigned int word = (unsigned int)src[off] | ((unsigned int)src[off + 1] << 8) | ((unsigned int)src[off + 2] << 16) | ((unsigned int)src[off + 3] << 24);
+      *reinterpret_cast<unsigned int*>(frames_out + a) = word;
+    }
+    if (k == 0) {
+      for (size_t p = g0; p < a0 && p < g1; ++p) frames_out[p] = src[p - g0];
+      const size_t tail = a0 + ((g1 > a0 ? g1 - a0 : 0) & ~(size_t)3);
+      for (size_t p = tail > g0 ? tail : g0; p < g1; ++p) if (p >= a0) frames_out[p] = src[p - g0];
+    }
+  }
+}
+
+}  // namespace nmf

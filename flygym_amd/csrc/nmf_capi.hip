@@ -17,6 +17,7 @@
 #include "nmf_step.hip"
 #include "nmf_sensors.hip"
 #include "nmf_eyes.hip"
+#include "nmf_camera.hip"
 #include "nmf_replay.hip"
 
 namespace {
@@ -1151,6 +1152,130 @@ extern "C" int nmf_eye_render_planned(nmf_batch* b, const nmf_eye_params* p, con
   if (A.terrain_kind != 0) { if (A.sampled) NMF_EYE_LAUNCH(true, true, false); else if (frames_out_dev) NMF_EYE_LAUNCH(false, true, true); else NMF_EYE_LAUNCH(false, true, false); }
   else { if (A.sampled) NMF_EYE_LAUNCH(true, false, false); else if (frames_out_dev) NMF_EYE_LAUNCH(false, false, true); else NMF_EYE_LAUNCH(false, false, false); }
 #undef NMF_EYE_LAUNCH
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// ---- batch camera renderer (nmf_camera.hip) ----
+// Everything a render needs besides the batch's poses and the caller's spheres: an explicit handle with its own device copies.
+struct nmf_camera_plan {
+  const nmf_batch* batch = nullptr;
+  int device = 0, n_cameras = 0, n_selected = 0, n_caps = 0;
+  nmf::CamArgs args{};
+  bool spheres_per_world = false;
+  nmf::CamView* views = nullptr; int* world_ids = nullptr; int* cap_seg = nullptr; float* cap_geom = nullptr; unsigned int* cap_rgb = nullptr;
+  std::vector<void*> allocs;
+};
+
+extern "C" size_t nmf_camera_params_size(void) { return sizeof(nmf_camera_params); }
+
+extern "C" void nmf_camera_plan_destroy(nmf_camera_plan* P) {
+  if (!P) return;
+  DeviceGuard guard(P->device);
+  for (void* q : P->allocs) (void)hipFree(q);      // (hipFree waits for the kernels that read them)
+  delete P;
+}
+
+static int fill_camera_plan(nmf_camera_plan* P, const nmf_batch* b, const nmf_camera_params* p, int n_cameras, const int32_t* world_ids, int n_selected,
+                            const int32_t* cap_seg, const float* cap_geom, const uint8_t* cap_rgb, int n_caps) {
+  const nmf_model* m = b->model;
+  if (n_cameras < 1 || n_cameras > NMF_CAMERA_MAX) return fail("nmf_camera_plan_create: need 1 <= n_cameras <= 8");
+  if (p->height < 1 || p->width < 1 || (int64_t)p->height * p->width > (1 << 26)) return fail("nmf_camera_plan_create: height and width must be at least 1 (and height * width at most 2^26)");
+  if (!world_ids || n_selected < 1) return fail("nmf_camera_plan_create: at least one world must be selected");
+  std::vector<char> seen((size_t)b->n_worlds, 0);
+  for (int i = 0; i < n_selected; ++i) {
+    if (world_ids[i] < 0 || world_ids[i] >= b->n_worlds) return fail("nmf_camera_plan_create: world id " + std::to_string(world_ids[i]) + " is outside [0, " + std::to_string(b->n_worlds) + ")");
+    if (seen[(size_t)world_ids[i]]) return fail("nmf_camera_plan_create: world id " + std::to_string(world_ids[i]) + " is selected twice");
+    seen[(size_t)world_ids[i]] = 1;
+  }
+  if (n_caps < 0 || n_caps > NMF_CAMERA_MAX_CAPSULES || (n_caps > 0 && (!cap_seg || !cap_geom || !cap_rgb))) return fail("nmf_camera_plan_create: bad capsule list (at most 72)");
+  for (int c = 0; c < n_caps; ++c) {
+    if (cap_seg[c] < 0 || cap_seg[c] >= m->nseg) return fail("nmf_camera_plan_create: capsule segment out of range");
+    if (!(cap_geom[7 * c + 6] > 0.f)) return fail("nmf_camera_plan_create: a capsule needs a positive radius");
+  }
+  if (p->n_spheres < 0 || p->n_spheres > nmf::kMaxSpheres) return fail("nmf_camera_plan_create: at most 8 spheres");
+  if (!(p->checker_size > 0.f)) return fail("nmf_camera_plan_create: bad checker size");
+  if (!(p->ambient >= 0.f) || !(p->diffuse >= 0.f)) return fail("nmf_camera_plan_create: the light terms must not be negative");
+  if (b->dm.plane[0] != 0.f || b->dm.plane[1] != 0.f || b->dm.plane[2] != 1.f) return fail("nmf_camera_plan_create: the ground plane must be z-up");
+  std::vector<nmf::CamView> views((size_t)n_cameras);
+  for (int c = 0; c < n_cameras; ++c) {
+    const nmf_camera_view& v = p->cam[c];
+    if (v.mode != NMF_CAMERA_FIXED && v.mode != NMF_CAMERA_TRACK) return fail("nmf_camera_plan_create: camera mode must be NMF_CAMERA_FIXED or NMF_CAMERA_TRACK");
+    if (v.mode == NMF_CAMERA_TRACK && (v.track_seg < 0 || v.track_seg >= m->nseg)) return fail("nmf_camera_plan_create: tracked segment out of range");
+    if (!(v.fovy_deg > 0.f) || !(v.fovy_deg < 180.f)) return fail("nmf_camera_plan_create: need 0 < fovy < 180 degrees");
+    for (int i = 0; i < 3; ++i)          // orthonormal columns
+      for (int j = i; j < 3; ++j) {
+        const double dd = (double)v.rot[i] * v.rot[j] + (double)v.rot[3 + i] * v.rot[3 + j] + (double)v.rot[6 + i] * v.rot[6 + j];
+        if (!(std::fabs(dd - (i == j ? 1.0 : 0.0)) < 1e-4)) return fail("nmf_camera_plan_create: the camera rotation must be orthonormal");
+      }
+    views[c].mode = v.mode; views[c].seg = v.mode == NMF_CAMERA_TRACK ? v.track_seg : 0;
+    for (int i = 0; i < 3; ++i) views[c].pos[i] = v.pos[i];
+    for (int i = 0; i < 9; ++i) views[c].rot[i] = v.rot[i];
+    views[c].tan_px = (float)(std::tan(0.5 * (double)v.fovy_deg * 3.14159265358979323846 / 180.0) / (0.5 * (double)p->height));
+  }
+  nmf::CamArgs& A = P->args;
+  A.height = p->height; A.width = p->width; A.tiles_x = (p->width + nmf::kCamTile - 1) / nmf::kCamTile;
+  A.ambient = p->ambient; A.diffuse = p->diffuse;
+  A.checker_size = p->checker_size; A.ground_z = b->dm.plane[3];
+  A.n_spheres = p->n_spheres; A.sphere_stride = p->spheres_per_world ? 4 * p->n_spheres : 0;
+  A.terrain_kind = p->terrain_relief ? b->dm.terrain_type : 0;
+  for (int k = 0; k < 5; ++k) A.terrain[k] = b->dm.terrain[k];
+  A.n_caps = n_caps;
+  for (int c = 0; c < 4; ++c) {
+    A.rgb[0][c] = c < 3 ? p->sky_rgb[c] : 0; A.rgb[1][c] = c < 3 ? p->ground_rgb[0][c] : 0; A.rgb[2][c] = c < 3 ? p->ground_rgb[1][c] : 0;
+    A.rgb[3][c] = c < 3 ? p->wall_rgb[c] : 0;
+    for (int s = 0; s < nmf::kMaxSpheres; ++s) A.rgb[4 + s][c] = c < 3 ? p->sphere_rgb[s][c] : 0;
+  }
+  P->spheres_per_world = p->spheres_per_world != 0;
+  P->n_cameras = n_cameras; P->n_selected = n_selected; P->n_caps = n_caps;
+  std::vector<unsigned int> rgbw((size_t)std::max(n_caps, 1), 0u);
+  for (int c = 0; c < n_caps; ++c) rgbw[(size_t)c] = (unsigned int)cap_rgb[3 * c] | ((unsigned int)cap_rgb[3 * c + 1] << 8) | ((unsigned int)cap_rgb[3 * c + 2] << 16);
+  auto upload = [&](const void* src, size_t bytes) -> void* {
+    void* q = nullptr;
+    if (hipMalloc(&q, std::max(bytes, (size_t)16)) != hipSuccess) return nullptr;
+    P->allocs.push_back(q);
+    if (bytes && hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    return q;
+  };
+  P->views = (nmf::CamView*)upload(views.data(), sizeof(nmf::CamView) * views.size());
+  P->world_ids = (int*)upload(world_ids, sizeof(int) * (size_t)n_selected);
+  P->cap_seg = (int*)upload(cap_seg, sizeof(int) * (size_t)n_caps);
+  P->cap_geom = (float*)upload(cap_geom, sizeof(float) * 7 * (size_t)n_caps);
+  P->cap_rgb = (unsigned int*)upload(rgbw.data(), sizeof(unsigned int) * (size_t)n_caps);
+  if (!P->views || !P->world_ids || !P->cap_seg || !P->cap_geom || !P->cap_rgb) return fail("nmf_camera_plan_create: out of device memory for the plan's copies");
+  HIP_OK(hipDeviceSynchronize());
+  return 0;
+}
+
+extern "C" nmf_camera_plan* nmf_camera_plan_create(nmf_batch* b, const nmf_camera_params* p, int n_cameras, const int32_t* world_ids, int n_selected,
+                                                   const int32_t* cap_seg, const float* cap_geom, const uint8_t* cap_rgb, int n_caps) {
+  if (!b || !p) { fail("nmf_camera_plan_create: null batch / params"); return nullptr; }
+  DeviceGuard guard(b->device);
+  if (guard.err != hipSuccess) { fail(std::string("hipSetDevice: ") + hipGetErrorString(guard.err)); return nullptr; }
+  nmf_camera_plan* P = new nmf_camera_plan();
+  P->batch = b; P->device = b->device;
+  if (fill_camera_plan(P, b, p, n_cameras, world_ids, n_selected, cap_seg, cap_geom, cap_rgb, n_caps) != 0) {
+    const std::string keep = g_err;
+    nmf_camera_plan_destroy(P);
+    g_err = keep;
+    return nullptr;
+  }
+  return P;
+}
+
+// Pure stream-ordered work: argument checks on the host, one kernel launch.
+extern "C" int nmf_camera_render(nmf_batch* b, const nmf_camera_plan* P, const float* spheres_dev, uint8_t* frames_out_dev, void* stream) {
+  if (!b || !P) return fail("nmf_camera_render: null batch / plan");
+  if (P->batch != b) return fail("nmf_camera_render: the plan was made for another batch");
+  if (!frames_out_dev) return fail("nmf_camera_render: nothing to write");
+  if (reinterpret_cast<uintptr_t>(frames_out_dev) & 15u) return fail("nmf_camera_render: frames must be 16-byte aligned");
+  if (P->args.n_spheres > 0 && !spheres_dev) return fail("nmf_camera_render: the plan has spheres, spheres_dev is required");
+  DEVICE_GUARD(b);
+  const nmf::CamArgs& A = P->args;
+  const unsigned tiles = (unsigned)(A.tiles_x * ((A.height + nmf::kCamTile - 1) / nmf::kCamTile));
+  hipLaunchKernelGGL(nmf::nmf_camera_kernel, dim3(tiles, (unsigned)P->n_cameras, (unsigned)P->n_selected), dim3(nmf::kCamThreads), 0, (hipStream_t)stream, A,
+                     P->views, P->world_ids, b->st.seg_xpos, b->st.seg_xquat, b->model->nseg, spheres_dev ? spheres_dev : b->st.seg_xpos,
+                     P->cap_seg, P->cap_geom, P->cap_rgb, frames_out_dev);
   HIP_OK(hipGetLastError());
   return 0;
 }

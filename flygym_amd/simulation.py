@@ -429,17 +429,56 @@ class HIPSimulation:
     def timestep(self) -> float:
         return float(self.model["opt_timestep"][0])
 
-    # ---- rendering hand-off (out of scope for the engine) ------------------
-    def set_renderer(self, *args, **kwargs):
-        raise NotImplementedError(
-            "rendering is outside the stepping engine: read poses with get_body_positions/"
-            "get_body_rotations and hand them to a renderer of your choice"
-        )
+    # ---- rendering ------------------------------------------------------------------------
+    def set_renderer(self, cameras=None, *, camera_res=(240, 320), playback_speed: float = 0.2, output_fps: int = 25,
+                     buffer_frames: bool = True, scene_option=None, worlds=None, use_gpu_batch_rendering: bool = False, **kwargs):
+        """Attach a renderer (the reference's signature, ``warp/simulation.py:266-342``).
+
+        ``use_gpu_batch_rendering=True`` builds and returns a :class:`flygym_amd.rendering.HIPBatchRenderer` of the worlds in
+        ``worlds`` (default: all) — the counterpart of the reference's ``WarpGPUBatchRenderer``; ``**kwargs`` go to it
+        (``scene``, ``ambient``, ``diffuse``, ``capsule_rgb``).  A ``scene_option`` raises ``RuntimeError`` as the reference's
+        batch renderer does.  ``use_gpu_batch_rendering=False`` is the reference's per-world MuJoCo OpenGL renderer, which
+        this engine does not have: ``NotImplementedError``."""
+        if not use_gpu_batch_rendering:
+            raise NotImplementedError(
+                "the per-world MuJoCo OpenGL renderer is outside this engine: pass use_gpu_batch_rendering=True for the batch "
+                "camera renderer, or read poses with get_body_positions/get_body_rotations and hand them to a renderer of "
+                "your choice"
+            )
+        if scene_option is not None:
+            raise RuntimeError("Custom scene options are not supported with the batch renderer.")
+        if cameras is None:
+            raise ValueError("At least one valid camera must be specified.")
+        from .rendering import HIPBatchRenderer
+
+        if self.renderer is not None:
+            self.renderer.close()
+        self.renderer = HIPBatchRenderer(self, cameras, worlds=worlds, camera_res=camera_res, playback_speed=playback_speed,
+                                         output_fps=output_fps, buffer_frames=buffer_frames, **kwargs)
+        return self.renderer
 
     def render_as_needed(self):
         if self.renderer is None:
             return {}
         return self.renderer.render_as_needed(self)
+
+    def render_as_needed_with_profile(self):
+        """:meth:`render_as_needed`, timed for the performance report (reference ``warp/simulation.py:344-350`` brackets the
+        call with ``perf_counter_ns``; a render here is an asynchronous launch, so the call is bracketed by device events and
+        the host waits for the frame — profiling, not the hot loop)."""
+        if self.renderer is None:
+            return {}
+        t = self._torch
+        e0, e1 = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
+        stream = t.cuda.current_stream(self.device)
+        e0.record(stream)
+        rendered = self.renderer.render_as_needed(self)
+        e1.record(stream)
+        if rendered:
+            e1.synchronize()
+            self._total_render_time_ns += int(e0.elapsed_time(e1) * 1e6)
+            self._frames_rendered += 1
+        return rendered
 
     def print_performance_report(self) -> None:
         """Report of the steps taken with :meth:`step_with_profile` (reference ``warp/simulation.py:344-367``)."""
@@ -544,6 +583,10 @@ class MultiFlyHIPSimulation(HIPSimulation):
     def replay_ids(self, fly_name: str, with_adhesion: bool = False): return self.sims[fly_name].replay_ids(fly_name, with_adhesion)
 
     # ---- one batch's business ------------------------------------------------------------
+    def set_renderer(self, *args, **kwargs):
+        raise NotImplementedError("worlds with several flies are out of scope for the batch renderer: one batch per fly means "
+                                  "compositing several batches' poses in one image")
+
     def _one_batch_only(self, what):
         raise AttributeError(f"{what} belongs to one fly's batch: use sim.for_fly(fly_name).{what} ({', '.join(self.sims)})")
 
@@ -693,7 +736,7 @@ class Simulation:
         return self.batch.render_as_needed()
 
     def render_as_needed_with_profile(self) -> bool:
-        return self.batch.render_as_needed()
+        return self.batch.render_as_needed_with_profile()
 
     def print_performance_report(self) -> None:
         self.batch.print_performance_report()

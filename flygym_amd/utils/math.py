@@ -104,3 +104,35 @@ class Rotation3D:
             h = 0.5 * float(self.values[3])
             return np.array([np.cos(h), *(ax * np.sin(h))])
         raise ValueError(f"cannot convert rotation format '{self.format}' to a quaternion")
+
+    def as_matrix(self) -> np.ndarray:
+        """3 x 3 rotation matrix (float64, orthonormal, right-handed) of every format MuJoCo's ``orientation`` attributes take:
+        ``quat`` (w, x, y, z), ``axisangle`` (axis, angle in radians), ``xyaxes`` (the frame's x axis, then a y axis that is
+        made orthogonal to it; z = x cross y), ``zaxis`` (the minimal rotation that takes (0, 0, 1) to the given direction),
+        ``euler`` (the model's compiler settings, reference ``mujoco_globals.yaml:3-4``: radians, ``eulerseq: XYZ`` — rotations
+        about the fixed parent axes x, then y, then z).  For a camera the columns are its right, up and back axes."""
+        v = np.asarray(self.values, dtype=np.float64)
+        if self.format in ("quat", "axisangle"):
+            w, x, y, z = self.as_quat()
+            return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                             [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                             [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+        if self.format == "xyaxes":
+            x = v[:3] / np.linalg.norm(v[:3])
+            y = v[3:] - (v[3:] @ x) * x
+            y = y / np.linalg.norm(y)
+            return np.stack([x, y, np.cross(x, y)], axis=1)
+        if self.format == "zaxis":
+            z = v / np.linalg.norm(v)
+            axis = np.cross([0.0, 0.0, 1.0], z)
+            s, c = np.linalg.norm(axis), z[2]
+            if s < 1e-12:
+                return np.eye(3) if c > 0 else np.diag([1.0, -1.0, -1.0])
+            k = axis / s
+            K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+            return np.eye(3) + s * K + (1 - c) * (K @ K)
+        cx, sx, cy, sy, cz, sz = np.cos(v[0]), np.sin(v[0]), np.cos(v[1]), np.sin(v[1]), np.cos(v[2]), np.sin(v[2])
+        rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+        ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+        rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+        return rz @ ry @ rx

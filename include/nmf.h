@@ -25,6 +25,7 @@ extern "C" {
 typedef struct nmf_model nmf_model;
 typedef struct nmf_batch nmf_batch;
 typedef struct nmf_eye_plan nmf_eye_plan;
+typedef struct nmf_camera_plan nmf_camera_plan;
 
 /* Per-world fields addressable through nmf_field_ptr / nmf_gather_* */
 enum nmf_field {
@@ -277,6 +278,59 @@ int nmf_eye_render_planned(nmf_batch* batch, const nmf_eye_params* params, const
 int nmf_eye_render(nmf_batch* batch, const nmf_eye_params* params, const float* spheres_dev,
                    const int32_t* capsule_seg_dev, const float* capsule_geom_dev, const int16_t* id_map_dev, const void* plan_dev, const uint8_t* pale_dev, const float* inv_norm_dev,
                    int n_ommatidia, uint8_t* frames_out_dev, float* omm_out_dev, void* stream);
+
+/* Batch camera renderer for selected worlds of a batch: the camera a person looks through.  Replaces the reference's
+ * WarpGPUBatchRenderer (warp/rendering.py:279-341: mjw.create_render_context once, then mjw.refit_bvh + mjw.render +
+ * get_rgb_selected_worlds_and_cameras per frame; attached by GPUSimulation.set_renderer, warp/simulation.py:266-342).
+ * Build-defined (specification tests/camera_spec.py): pinhole cameras — pixel (row, col) has the
+ * camera-frame ray (u, -v, -1) normalised, u = (col + 0.5 - W/2) t, v = (row + 0.5 - H/2) t, t = tan(fovy/2) / (H/2);
+ * x right, y up, looking along -z — the eye renderer's scene plus the whole fly as capsules with a colour each, one
+ * directional light from straight above: colour = base * (ambient + diffuse * max(0, n_z)), rounded to uint8.
+ * Reads the segment poses of the last nmf_step / nmf_reset. */
+#define NMF_CAMERA_MAX 8          /* cameras per plan */
+#define NMF_CAMERA_MAX_CAPSULES 72
+#define NMF_CAMERA_FIXED 0        /* pos and rot are world coordinates                                                   */
+#define NMF_CAMERA_TRACK 1        /* position = position of segment track_seg + pos; orientation constant in the world
+                                     (MuJoCo's "track" for a camera whose parent is that segment)                        */
+typedef struct nmf_camera_view {
+  int32_t mode;                 /* NMF_CAMERA_FIXED / NMF_CAMERA_TRACK                                                   */
+  int32_t track_seg;            /* tracked segment (index into the batch's segment order); ignored for fixed cameras    */
+  float fovy_deg;               /* full vertical field of view, 0 < fovy < 180                                          */
+  float pos[3];                 /* world position (fixed) or offset from the tracked segment (track)                    */
+  float rot[9];                 /* camera axes in the world, row-major, columns right / up / back (orthonormal)        */
+} nmf_camera_view;
+
+typedef struct nmf_camera_params {
+  int32_t height, width;        /* frame size in pixels, each >= 1                                                       */
+  nmf_camera_view cam[NMF_CAMERA_MAX];
+  float ambient, diffuse;       /* light terms                                                                           */
+  float checker_size;           /* the nmf_eye_params scene fields, with the same meaning                               */
+  uint8_t sky_rgb[4], ground_rgb[2][4], sphere_rgb[8][4];
+  int32_t n_spheres, spheres_per_world;
+  uint8_t wall_rgb[4];
+  int32_t terrain_relief;
+} nmf_camera_params;
+
+/* sizeof(nmf_camera_params) as this library was compiled (as nmf_eye_params_size). */
+size_t nmf_camera_params_size(void);
+
+/* Replaces WarpGPUBatchRenderer._render_setup_impl (warp/rendering.py:282-309: the world / camera id arrays and
+ * mjw.create_render_context).  An explicit handle: takes HOST arrays — params, world_ids[n_selected] (each in
+ * [0, n_worlds), distinct), cap_seg[n_caps] (< the batch's segment count), cap_geom[n_caps][7] (end points p0, p1 in the
+ * segment frame, radius), cap_rgb[n_caps][3] — validates them, and owns device copies.  1 <= n_cameras <= NMF_CAMERA_MAX,
+ * 0 <= n_caps <= NMF_CAMERA_MAX_CAPSULES, n_selected >= 1.  NOT stream-ordered (allocations and synchronous uploads, once);
+ * must not be called inside a stream capture.  The plan belongs to the batch it was made for.  NULL on error (nmf_last_error). */
+nmf_camera_plan* nmf_camera_plan_create(nmf_batch* batch, const nmf_camera_params* params, int n_cameras,
+                                        const int32_t* world_ids, int n_selected, const int32_t* cap_seg, const float* cap_geom,
+                                        const uint8_t* cap_rgb, int n_caps);
+void nmf_camera_plan_destroy(nmf_camera_plan* plan);
+
+/* Replaces WarpGPUBatchRenderer._render_impl (warp/rendering.py:311-321).  Argument checks and ONE kernel launch on
+ * `stream` (the stream the batch is stepped on): no allocation, no host synchronisation, hipGraph-capturable — nmf_step +
+ * nmf_camera_render capture as one graph.  spheres_dev: NULL when the plan has no spheres, else float32 (x, y, z, radius)
+ * [n_spheres][4], or [n_worlds][n_spheres][4] with spheres_per_world = 1.  frames_out_dev: uint8
+ * [n_selected][n_cameras][height][width][3], 16-byte aligned. */
+int nmf_camera_render(nmf_batch* batch, const nmf_camera_plan* plan, const float* spheres_dev, uint8_t* frames_out_dev, void* stream);
 
 /* Odor intensity at n_sensors points rigidly attached to named segments (sensor_seg = index into the
  * batch's segment order, sensor_rel = offset in the segment frame): out[w][d][k] = sum_s peak[s][d] / dist^2.
