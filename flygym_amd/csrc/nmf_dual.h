@@ -346,44 +346,44 @@ __device__ __forceinline__ int dual_solve(FlyLds<TP>& s, const GModel& m, int la
   SUB(43);
   // ---- G = Gram matrix of the direction responses, every unordered pair of contacts once: in round t the quad of contact c
   // takes contact c - t (cyclically over the ncon contacts), whose three vectors come through ds_bpermute — lane (c, k) fetches
-  // direction k — and pairs every one of them with its own: the partner's other two directions reach the lane through a
-  // quad permutation (k -> k + p mod 3; lane 3 of a quad carries a copy of t2 and stores nothing).  ncon / 2 + 1 rounds.
+  // direction k.  ncon / 2 + 1 rounds.  The 3 x 3 block of a pair is a sum of 6 + NDL outer products, and the quad-per-contact
+  // layout is the one v_mfma_f32_4x4x1_16B_f32 has (sixteen independent 4 x 4 blocks, block = four consecutive lanes): with
+  // A = the lane's own number and B = the fetched one, lane (c, k) register i receives <direction i of c, direction k of c2> —
+  // one instruction per root axis / hinge, fed as the numbers arrive, no permutation inside the quad.  Lane 3 of a quad
+  // carries a copy of t2: row 3 and column 3 of its block are never stored.
+  // The order of the sum is the one this block has always been compiled to (under -fassociative-math the compiler folds
+  // `root + (same ? leg : 0)` of two multiply-add chains into ONE chain): the leg terms first, zero where the pair is not on
+  // one leg, then the six root terms on top of that.  The matrix pipe rounds once per multiply-add like v_fma_f32
+  // (scripts/micro/mfma_gram_probe.hip, tests/test_mfma_gram_probe.py), so every entry of G keeps its bits.  (The first
+  // term is fma(a, b, +0) where it was a v_mul: the same number, but a product of -0 becomes +0.  That can differ in G only
+  // if all 6 + NDL products of an entry are zero — no contact has such a response — and the build is -fno-signed-zeros anyway.
+  // The accumulator starts from the inline constant 0: a register holding -0 costs the hybrid kernels spills.)
+  // The leg terms couple contacts of one leg only: a round without such a pair (wave-uniform) skips their fetches.
   {
-    const int kd = k < 3 ? k : 2;
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    static_assert(kDualMaxCon<TP> <= 16, "one quad of the wave per contact: a 4 x 4 block of the matrix instruction each");
     const int half = ncon >> 1;
     for (int t = 0; t <= half; ++t) {
       int c2 = cc - t;
       c2 = c2 < 0 ? c2 + ncon : c2;
       const int src = (on ? 4 * c2 + k : lane) << 2;
       auto from = [&](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src, __builtin_bit_cast(int, v))); };
-      float pr[6], pl[NDL];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) pr[i] = from(ur[i]);
-#pragma unroll
-      for (int d = 0; d < NDL; ++d) pl[d] = from(ul[d]);
       const bool same = __builtin_amdgcn_ds_bpermute(src, leg) == leg;
       const bool ge = cc >= c2;
-      int base = ge ? 9 * (cc * (cc + 1) / 2 + c2) + 3 * kd : 9 * (c2 * (c2 + 1) / 2 + cc) + kd;
-      const int stride = ge ? 1 : 3;
+      int base = ge ? 9 * (cc * (cc + 1) / 2 + c2) + k : 9 * (c2 * (c2 + 1) / 2 + cc) + 3 * k;      // register i: + stride i
+      const int stride = ge ? 3 : 1;
       asm("" : "+v"(base));
-      // (Round 5 tried to skip the leg parts — NDL of the 6 + NDL numbers, which couple contacts of one leg only — in the rounds
-      // that cannot pair two contacts of a leg: any root-only variant of this round, as a second instantiation or under a
-      // wave-uniform branch, raised the kernel's spilled registers from 12 to 50 and cost 6 %.)
-      static_for<3>([&](auto PP) {
-        constexpr int p = decltype(PP)::value;
-        auto rot = [&](float v) {      // the fetched vector of direction (k + p) mod 3
-          if constexpr (p == 0) return v; else if constexpr (p == 1) return NMF_DPP(v, 0xC9); else return NMF_DPP(v, 0xD2);
-        };
-        float a = rot(pr[0]) * ur[0];
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      if (__ballot(on && same) != 0ull) {
+        f32x4 al = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int i = 1; i < 6; ++i) a = fmaf(rot(pr[i]), ur[i], a);
-        float bl = rot(pl[0]) * ul[0];
+        for (int d = 0; d < NDL; ++d) al = __builtin_amdgcn_mfma_f32_4x4x1f32(ul[d], from(ul[d]), al, 0, 0, 0);
 #pragma unroll
-        for (int d = 1; d < NDL; ++d) bl = fmaf(rot(pl[d]), ul[d], bl);
-        a += same ? bl : 0.f;
-        const int d2 = kd + p >= 3 ? kd + p - 3 : kd + p;
-        if (on && k < 3) Gm[base + stride * d2] = a;
-      });
+        for (int i = 0; i < 4; ++i) acc[i] = same ? al[i] : 0.f;      // (all four: selecting three only costs the hybrid kernels registers)
+      }
+#pragma unroll
+      for (int i = 0; i < 6; ++i) acc = __builtin_amdgcn_mfma_f32_4x4x1f32(ur[i], from(ur[i]), acc, 0, 0, 0);
+      if (on && k < 3) { Gm[base] = acc[0]; Gm[base + stride] = acc[1]; Gm[base + 2 * stride] = acc[2]; }
     }
   }
   WSYNC();
