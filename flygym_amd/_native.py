@@ -10,6 +10,7 @@ import ctypes
 import os
 import subprocess
 from pathlib import Path
+from typing import Sequence
 
 PKG = Path(__file__).resolve().parent
 # NMF_HIP_LIB: load another build of the same ABI (kernel A/B experiments: scripts/build_variant.sh); the default is the
@@ -56,10 +57,14 @@ INFO_KEYS = ("kernel_family", "terrain_kernel", "tether_kernel", "contact_space_
              "contact_capacity", "kernel_lds_bytes", "kernel_vgprs")
 
 
+def build_inputs() -> list[Path]:
+    """Every file a change of which makes the built library stale: the whole of csrc/, the C ABI, and this file (the flags)."""
+    return [*sorted(CSRC.glob("*.hip")), *sorted(CSRC.glob("*.h")), INCLUDE / "nmf.h", Path(__file__)]
+
+
 def build(force: bool = False, verbose: bool = False) -> Path:
     """Compile the HIP engine for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [CSRC / "nmf_capi.hip", CSRC / "nmf_step.hip", CSRC / "nmf_sensors.hip", CSRC / "nmf_eyes.hip", CSRC / "nmf_camera.hip", CSRC / "nmf_replay.hip", CSRC / "nmf_device.h", CSRC / "nmf_tree.h", CSRC / "nmf_dual.h",
-            INCLUDE / "nmf.h", Path(__file__)]   # this file holds the compiler flags
+    srcs = build_inputs()
     if os.environ.get("NMF_HIP_LIB"):
         return LIB_PATH                       # an externally built variant: nothing to compile here
     def fresh():
@@ -82,7 +87,9 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         lock.close()
 
 
-def _compile(verbose: bool) -> Path:
+def compile_command(out: Path, extra: Sequence[str] = ()) -> list[str]:
+    """The hipcc invocation that builds the engine into ``out``: the one place that spells its flags (``extra``: -D options of
+    diagnostic / A-B builds, scripts/build_variant.sh and scripts/stage_profile.py)."""
     # -fno-slp-vectorize: the SLP vectoriser packs the 6-vector arithmetic into v_pk_* pairs and pays for it in v_mov
     # shuffles and register pressure (12 spilled VGPRs); scalar code is 9 % faster on the step kernel.  The iterative
     # ILP scheduler interleaves the independent chains of the unrolled sweeps better than the default (+5 %).
@@ -91,13 +98,16 @@ def _compile(verbose: bool) -> Path:
     # only transcendental of the step, the joint-angle sincos, is the kernel's own polynomial (nmf_device.h).
     # No atomic optimizer: the kernels' atomics are one-lane ticket / counter operations; the optimizer rewrites a returning
     # one into a wave-wide form that waits for the value at once (the chunk scheduler requests its ticket ahead of use).
-    tmp = LIB_PATH.with_name(LIB_PATH.name + f".{os.getpid()}.tmp")
-    cmd = [
+    return [
         "hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp",
-        *MATH_FLAGS, "-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-fPIC", "-shared",
-        f"-I{INCLUDE}", f"-I{CSRC}", str(CSRC / "nmf_capi.hip"), "-o", str(tmp),
+        *MATH_FLAGS, "-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-fPIC", "-shared", *extra,
+        f"-I{INCLUDE}", f"-I{CSRC}", str(CSRC / "nmf_capi.hip"), "-o", str(out),
     ]
-    res = subprocess.run(cmd, capture_output=True, text=True)
+
+
+def _compile(verbose: bool) -> Path:
+    tmp = LIB_PATH.with_name(LIB_PATH.name + f".{os.getpid()}.tmp")
+    res = subprocess.run(compile_command(tmp), capture_output=True, text=True)
     if res.returncode != 0:
         tmp.unlink(missing_ok=True)
         raise NativeError("hipcc failed:\n" + res.stderr[-4000:])

@@ -447,7 +447,7 @@ def compile_world(world) -> CompiledModel:
             else:
                 affine_dofs.add(dof_index[a["jointdof"]])
         if a["kind"] in _GENERAL_KINDS or a["kind"] == "affine":
-            # the stepping kernel's affine pass sees a motor of gain 0 without a force limit; the general pass (nmf_step.hip
+            # the stepping kernel's affine pass sees a motor of gain 0 without a force limit; the general pass (nmf_step_actuation.h
             # actuation_general, oracle general_actuator) computes the force from the act_general row
             general_rows[len(act_type)] = _general_row(a, dof_index[a["jointdof"]])
             act_type.append(ACT_MOTOR)

@@ -1,7 +1,7 @@
 // nmf_capi.hip — host side of libnmf_hip.so: the C ABI declared in include/nmf.h.
 //
 // Owns device memory for the model constants and the per-world state, launches the fused step
-// kernel (nmf_step.hip) and the gather/scatter kernels.  No torch types, no host sync on the
+// kernel (nmf_step.hip) and the gather/scatter kernels (nmf_batch_ops.hip).  No torch types, no host sync on the
 // stepping path.
 #include <hip/hip_runtime.h>
 
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "nmf.h"
+#include "nmf_batch_ops.hip"
 #include "nmf_step.hip"
 #include "nmf_sensors.hip"
 #include "nmf_eyes.hip"
@@ -1335,7 +1336,7 @@ extern "C" int nmf_replay_resample(const float* clip_dev, int n_frames, int n_co
 }
 
 #ifdef NMF_SCHED_TRACE
-// diagnostic build only: per-workgroup schedule trace of the last stepping launch (see nmf_step.hip)
+// diagnostic build only: per-workgroup schedule trace of the last stepping launch (see nmf_step_diag.h)
 extern "C" int nmf_debug_sched_trace(unsigned long long* out, int n_groups) {
   if (hipDeviceSynchronize() != hipSuccess) return -1;
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(nmf::g_sched_trace), sizeof(unsigned long long) * 8 * (size_t)std::min(n_groups, 4096)) != hipSuccess) return -1;

@@ -147,7 +147,7 @@ struct DevModel {
   int max_contacts;
   const NMF_G float *act_gain, *act_bias, *act_forcerange, *act_ctrlrange;
   // [nu][32] or nullptr: MuJoCo's general actuator for the actuators the affine pass does not cover (intvelocity, damper,
-  // cylinder, muscle; later actuators of a shared dof) — flygym_amd/compiler/model.py::_general_row, nmf_step.hip actuation_general
+  // cylinder, muscle; later actuators of a shared dof) — flygym_amd/compiler/model.py::_general_row, nmf_step_actuation.h actuation_general
   const NMF_G float* act_general;
   const NMF_G float *key_qpos, *key_ctrl;
   const NMF_G int *geom_body, *geom_type, *geom_hulladr, *geom_hullnum, *geom_sensor;
@@ -185,11 +185,11 @@ struct DevState {
   // goes to ring[(step + 1) / obs_every - 1][world][.], rows ring_stride floats apart
   float* ring;
   int ring_stride, obs_every, ring_nj, ring_nact;
-  // CPU flavour (noslip iterations on): per world the scratch of the primal path's noslip pass (nmf_step.hip::noslip_primal);
+  // CPU flavour (noslip iterations on): per world the scratch of the primal path's noslip pass (nmf_step_noslip.h::noslip_primal);
   // nullptr on the batched path
   float* noslip_buf;
   // kernels whose leg factors do not fit LDS (ALL_POSSIBLE): per workgroup of a stepping launch the contact-space solve's leg
-  // factors (nmf_step.hip kDualGlob); nullptr elsewhere
+  // factors (nmf_step_lds.h kDualGlob); nullptr elsewhere
   float* dual_scratch;
   int chunk_start[17];        // chunk c covers steps chunk_start[c] .. chunk_start[c + 1] - 1 (lengths shrink towards the end)
 };

@@ -1,5 +1,5 @@
 // nmf_dual.h — the constraint solve in contact space (leg-chain kernels: a free root + identical leg chains; and the hybrid
-// kernels whose data fit, see kDualS / kDualH in nmf_step.hip).
+// kernels whose data fit, see kDualS / kDualH in nmf_step_lds.h).
 //
 // Same problem and same optimum as the primal loop in physics_forward (MuJoCo's Newton solver with exact line search,
 // reference src/flygym/assets/model/mujoco_globals.yaml:13-14 behind mujoco_warp.step, src/flygym/warp/simulation.py:260-263)
@@ -41,7 +41,7 @@
 
 namespace nmf {
 
-// (the factors' homes: dual_leg / dual_root / dual_aref / dual_acc in nmf_step.hip)
+// (the factors' homes: dual_leg / dual_root / dual_aref / dual_acc in nmf_step_aba.h)
 // G, block (c, c') with c >= c' at 9 (c (c + 1) / 2 + c'), entry [direction of c][direction of c'] (0 normal, 1 / 2 tangents):
 // over Ib..W (+ dual_pad); hybrid kernels: over T..W (Ib is their one copy of the inertias)
 template <class TP>
@@ -206,7 +206,7 @@ __device__ __noinline__ float dual_noslip_cold(FlyLds<TP>& s, const GModel& m, i
   return dual_noslip<TP>(s, m, lane, ncon, frow, j0, R, smu);
 }
 
-// How a solve ended (SolveReport bits, nmf_step.hip) and what the elimination it ended on violates: for every end but the
+// How a solve ended (SolveReport bits, nmf_step_lds.h) and what the elimination it ended on violates: for every end but the
 // exact one the rows in (target's sign pattern) xor (pivot set) are the target's KKT violations — the largest |residual| among
 // them relative to the largest |residual| of all rows goes out as `resid` (0 = exact).
 // aref of row (contact c, pyramid row k) is expected in s.vB[4 c + k] (physics_forward puts it there).  Leaves qacc and the

@@ -56,7 +56,7 @@ struct EyeArgs {
 };
 
 // constant-height cell of h(x, y) that holds (x, y): bounds (+-inf where unbounded) and level — the same arithmetic as
-// the physics' terrain_height (nmf_step.hip) and as oracle/sensors_oracle.py::terrain_cell
+// the physics' terrain_height (nmf_step_collision.h) and as oracle/sensors_oracle.py::terrain_cell
 struct TerrainCell { float x0, x1, y0, y1, h; };
 __device__ __forceinline__ TerrainCell cell_gapped(float block, float gap, float depth, float x) {
   const float period = block + gap;

@@ -1,5 +1,6 @@
 // nmf_tree.h — sweeps of the stepping kernel for a general kinematic tree (any JointPreset: ALL_BIOLOGICAL nv = 132,
-// ALL_POSSIBLE nv = 210, custom skeletons), included by nmf_step.hip.
+// ALL_POSSIBLE nv = 210, custom skeletons), included by nmf_step.hip after the stage headers (nmf_step_*.h): the
+// articulated-body passes here are built from aba_step / add_contact_K_row of nmf_step_aba.h.
 //
 // The chain-star kernels (Topo<...>: identical leg chains hanging off the root) unroll their sweeps at compile time with
 // (leg, row) lanes.  A general tree has no such regularity, so here every sweep walks the tree LEVEL BY LEVEL (bodies in

@@ -650,7 +650,7 @@ class Simulation:
     The CPU class's noslip post-pass (``option/noslip_iterations = 5``, ``mujoco_globals.yaml:15``) runs here too, on every
     skeleton and world: inside the contact-space solve where a step takes it (leg-chain skeletons and ALL_BIOLOGICAL with up
     to 16 / 13 contacts on the legs), else after the primal Newton loop with ``A = J M^-1 J^T`` built by one articulated-body
-    solve per constraint row (``csrc/nmf_step.hip::noslip_primal`` — one world: cost is no object).  A step with contacts
+    solve per constraint row (``csrc/nmf_step_noslip.h::noslip_primal`` — one world: cost is no object).  A step with contacts
     that went without the pass would be counted (``get_solver_exits()["noslip_skipped"]``); none does.
     """
 

@@ -1,4 +1,7 @@
-"""LDS / VGPR / spill figures of every stepping-kernel instantiation in the built library (no GPU needed)."""
+"""LDS / VGPR / spill figures of every stepping-kernel instantiation in the built library (no GPU needed).
+
+--text-sha256: print the SHA-256 of the gfx950 code object's .text section instead (same machine code <=> same digest)."""
+import hashlib
 import re
 import struct
 import subprocess
@@ -6,7 +9,8 @@ import sys
 import tempfile
 from pathlib import Path
 
-so = Path(sys.argv[1] if len(sys.argv) > 1 else Path(__file__).resolve().parents[1] / "flygym_amd" / "libnmf_hip.so")
+paths = [a for a in sys.argv[1:] if not a.startswith("--")]
+so = Path(paths[0] if paths else Path(__file__).resolve().parents[1] / "flygym_amd" / "libnmf_hip.so")
 d = so.read_bytes()
 i = d.find(b"__CLANG_OFFLOAD_BUNDLE__")
 n = struct.unpack_from("<Q", d, i + 24)[0]
@@ -19,6 +23,10 @@ with tempfile.TemporaryDirectory() as tmp:
         off += tl
         if "gfx950" in triple:
             (Path(tmp) / "co.elf").write_bytes(d[i + o:i + o + s])
+    if "--text-sha256" in sys.argv:
+        subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objcopy", "-O", "binary", "--only-section=.text", f"{tmp}/co.elf", f"{tmp}/text.bin"], check=True)
+        print(hashlib.sha256((Path(tmp) / "text.bin").read_bytes()).hexdigest())
+        sys.exit(0)
     out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", f"{tmp}/co.elf"], capture_output=True, text=True).stdout
 for blk in out.split("- .agpr_count")[1:]:
     name = re.search(r"\.name:\s+(\S+)", blk).group(1)

@@ -8,9 +8,7 @@ from flygym_amd import _native
 lib_prof = ROOT / "build" / "libnmf_prof.so"      # (a diagnostic build: never beside the product library)
 lib_prof.parent.mkdir(exist_ok=True)
 if "--build" in sys.argv or not lib_prof.exists():
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp", *_native.MATH_FLAGS,
-                    "-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-fPIC", "-shared", "-DNMF_STAGE_PROFILE", *[a for a in sys.argv if a.startswith("-D")],
-                    f"-I{ROOT/'include'}", f"-I{ROOT/'flygym_amd/csrc'}", str(ROOT/"flygym_amd/csrc/nmf_capi.hip"), "-o", str(lib_prof)], check=True)
+    subprocess.run(_native.compile_command(lib_prof, ["-DNMF_STAGE_PROFILE", *[a for a in sys.argv if a.startswith("-D")]]), check=True)
     if "--build" in sys.argv: sys.exit(0)
 _native.LIB_PATH = lib_prof
 from flygym_amd import HIPSimulation, make_model

@@ -138,6 +138,15 @@ def test_abi_exports_every_declared_symbol():
         assert hasattr(lib, name), f"libnmf_hip.so does not export {name}"
 
 
+def test_build_freshness_covers_every_engine_source():
+    """A library older than ANY file of csrc/ (a header included) or than the C ABI is stale: build() compares against all of them."""
+    inputs = {p.resolve() for p in _native.build_inputs()}
+    sources = [p for p in _native.CSRC.rglob("*") if p.is_file()] + [_native.INCLUDE / "nmf.h"]
+    assert len(sources) > 10
+    for src in sources:
+        assert src.resolve() in inputs, f"_native.build() would not notice an edit of {src}"
+
+
 def test_abi_struct_layout_and_plan_size():
     """The ctypes mirror of nmf_eye_params has the layout the library was compiled with; plan buffer sizing."""
     from flygym_amd.vision import _EyeParams
