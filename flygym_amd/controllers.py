@@ -1,4 +1,5 @@
-"""Open-loop controllers that produce position-actuator targets for the batched engine.
+"""Controllers that produce position-actuator targets for the batched engine: the open-loop ``TripodCPG`` table builder and
+the closed-loop, steerable ``TurningCPG`` whose state lives on the GPU (at the end of this docstring).
 
 ``TripodCPG`` is the "position-actuated CPG tripod gait" of BASELINE config 2.  The reference snapshot has
 no CPG (flygym 2.0.1 dropped flygym 1.x's controllers), so this one is build-defined:
@@ -17,16 +18,25 @@ Leg adhesion driven by the gait (BASELINE config 5): ``stance_bins`` marks, per 
 which the claw is near its lowest point (forward kinematics of the cycle in the thorax frame); with
 ``adhesion=(stance, on, off)`` the table gets six more columns holding the adhesion control ``on`` in stance and
 ``off`` in swing.  The reference clamps adhesion controls to [1, 100] (``compose/fly.py:434-440``), so "off" is 1.
+
+``TurningCPG`` makes the same gait a small recurrent system that is advanced on the device between physics launches
+(``csrc/nmf_cpg.hip``; specification ``tests/cpg_spec.py``; build-defined like ``TripodCPG``, in the form of flygym 1.x's
+turning controller): six coupled phase oscillators per world with a phase (cycles, float64) and a magnitude each, and a per-world
+drive ``(d_left, d_right)`` — ``|d|`` is the magnitude a side's legs converge to, ``sign(d)`` the direction its phases run in.
+With the unit drive it reproduces ``TripodCPG.targets``; a weaker side shortens that side's strides and the fly turns towards it.
 """
 
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 
+from . import _native
 from .anatomy import LEGS, JointDOF
 from .replay import MotionSnippet
 
-__all__ = ["TripodCPG"]
+__all__ = ["TripodCPG", "TurningCPG"]
 
 TRIPOD_PHASE_BIAS = {"lf": 0.0, "rm": 0.0, "lh": 0.0, "rf": np.pi, "lm": np.pi, "rh": np.pi}
 
@@ -160,3 +170,152 @@ class TripodCPG:
             frac = (x - torch.floor(x)).to(torch.float32)
             out[w0:w0 + len(w)] = (1 - frac) * cyc[i0, cols] + frac * cyc[(i0 + 1) % self.n_bins, cols]
         return out
+
+
+class _CpgParams(ctypes.Structure):
+    """``nmf_cpg_params`` of include/nmf.h."""
+
+    _fields_ = [("n_pos", ctypes.c_int32), ("n_bins", ctypes.c_int32), ("frequency", ctypes.c_double), ("timestep", ctypes.c_double),
+                ("coupling", ctypes.c_float), ("convergence", ctypes.c_float), ("adhesion_on", ctypes.c_float),
+                ("adhesion_off", ctypes.c_float), ("table_steps", ctypes.c_int32)]
+
+
+class TurningCPG(TripodCPG):
+    """Closed-loop tripod CPG of one fly of a :class:`~flygym_amd.HIPSimulation`, advanced on the GPU (``nmf_cpg_advance``).
+
+    Per step and world (every right-hand side from the old state; the row is computed before the update)::
+
+        theta_l <- (theta_l + dt (frequency sign(d_side) + (1 / 2 pi) sum_{j != l} r_j coupling sin(2 pi (theta_j - theta_l) - (b_j - b_l)))) mod 1
+        r_l     <- r_l + dt convergence (|d_side| - r_l)
+        target[col] = c + (r_l - 1) (c - mean[col]),  c = the step cycle interpolated at theta_l
+
+    Args:
+        sim: the batch; for a world with several flies ``sim.for_fly(fly_name)``.
+        fly_name: the fly whose position (and adhesion) actuators the table drives.
+        frequency, coupling, convergence, n_phase_bins: the shared parameters.
+        adhesion: ``(on, off)`` or ``(on, off, threshold)`` appends six adhesion columns that follow ``stance_bins``.
+        table_steps: rows per world of the controller's own table: the most steps of one :meth:`advance`.
+
+    ``phase`` ``(n, 6)`` float64, ``magnitude`` ``(n, 6)`` float32 and ``drive`` ``(n, 2)`` float32 are zero-copy views of the
+    device state, writable between launches.  A new controller is reset: the tripod, world ``w`` at the phase offset ``w / n``.
+    """
+
+    def __init__(self, sim, fly_name: str, *, frequency: float = 12.0, coupling: float = 10.0, convergence: float = 20.0,
+                 n_phase_bins: int = 256, adhesion=None, table_steps: int = 64):
+        if hasattr(sim, "for_fly"):
+            raise ValueError(f"a world with several flies has one batch per fly: pass sim.for_fly({fly_name!r})")
+        if fly_name not in sim.world.fly_lookup:
+            raise ValueError(f"no fly named {fly_name!r} in this simulation ({', '.join(sim.world.fly_lookup)})")
+        if int(table_steps) < 1:
+            raise ValueError(f"table_steps must be at least 1, got {table_steps}")
+        if int(n_phase_bins) < 2:
+            raise ValueError(f"n_phase_bins must be at least 2, got {n_phase_bins}")
+        fly = sim.world.fly_lookup[fly_name]
+        super().__init__(fly.get_actuated_jointdofs_order("position"), sim.timestep, frequency=frequency, n_phase_bins=n_phase_bins)
+        self.sim, self.fly_name = sim, fly_name
+        self.coupling, self.convergence = float(coupling), float(convergence)
+        self.n_worlds, self.table_steps = int(sim.n_worlds), int(table_steps)
+        self.adhesion, self.stance = None, None
+        if adhesion is not None:
+            if len(adhesion) not in (2, 3):
+                raise ValueError(f"adhesion must be (on, off) or (on, off, threshold), got {adhesion!r}")
+            self.adhesion = (float(adhesion[0]), float(adhesion[1]))
+            self.stance = self.stance_bins(sim.model, fly, *([float(adhesion[2])] if len(adhesion) == 3 else []))
+        self.act_ids = sim.replay_ids(fly_name, with_adhesion=adhesion is not None)
+        n_pos = len(self.actuated_dofs)
+        self.n_act = n_pos + (6 if adhesion is not None else 0)
+        if int(self.act_ids.numel()) != self.n_act:
+            raise ValueError(f"the fly has {int(self.act_ids.numel())} actuators for a table of {self.n_act} columns")
+        lib = _native.lib()
+        if ctypes.sizeof(_CpgParams) != lib.nmf_cpg_params_size():
+            raise _native.NativeError("nmf_cpg_params layout mismatch between controllers.py and libnmf_hip.so")
+        on, off = self.adhesion or (0.0, 0.0)
+        self._params = _CpgParams(n_pos, self.n_bins, self.frequency, self.timestep, self.coupling, self.convergence, on, off,
+                                  self.table_steps)
+        cycle = np.ascontiguousarray(self.cycle, dtype=np.float32)
+        legs = np.ascontiguousarray(self.leg_of_dof, dtype=np.int32)
+        stance = None if self.stance is None else np.ascontiguousarray(self.stance, dtype=np.uint8)
+        self._h = lib.nmf_cpg_create(sim._batch_h, ctypes.byref(self._params), cycle.ctypes.data, legs.ctypes.data,
+                                     None if stance is None else stance.ctypes.data)
+        if not self._h:
+            raise _native.NativeError(lib.nmf_last_error().decode())
+        from .simulation import _tensor_from_ptr
+
+        t = sim._torch
+        views = []
+        for which, typestr in ((0, "<f8"), (1, "<f4"), (2, "<f4")):
+            width = ctypes.c_int32(0)
+            ptr = lib.nmf_cpg_field_ptr(self._h, which, ctypes.byref(width))
+            if not ptr:
+                raise _native.NativeError(lib.nmf_last_error().decode())
+            views.append(_tensor_from_ptr(t, ptr, (self.n_worlds, width.value), sim.device, typestr))
+        self.phase, self.magnitude, self.drive = views
+        self.table = t.zeros((self.n_worlds, self.table_steps, self.n_act), dtype=t.float32, device=sim.device)
+
+    # ---- lifecycle
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _native.lib().nmf_cpg_destroy(self._h)
+            self._h = None
+            self.phase = self.magnitude = self.drive = None        # (views of freed memory)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _handle(self):
+        if not getattr(self, "_h", None):
+            raise RuntimeError("the controller is closed")
+        return self._h
+
+    # ---- control
+    def set_drive(self, drive) -> None:
+        """``(n_worlds, 2)`` (left, right), numpy or torch: copied into :attr:`drive` on the simulation's stream."""
+        self._handle()
+        t = self.sim._torch
+        if not isinstance(drive, t.Tensor):
+            drive = t.as_tensor(np.array(drive, dtype=np.float32))
+        if tuple(drive.shape) != (self.n_worlds, 2):
+            raise ValueError(f"Expected a drive of shape ({self.n_worlds}, 2), but got {tuple(drive.shape)}")
+        self.drive.copy_(drive.to(device=self.sim.device, dtype=t.float32))
+
+    def reset(self, mask=None, first_world: int = 0, total_worlds: int | None = None) -> None:
+        """The worlds of ``mask`` (``(n_worlds,)`` bool, numpy or torch; default all) go back to the tripod with
+        ``theta_l = ((first_world + w) / total_worlds + b_l / 2 pi) mod 1``, ``r = 1``, ``drive = (1, 1)``; the others keep their
+        state.  Stream-ordered device work (no host sync)."""
+        h = self._handle()
+        t = self.sim._torch
+        total = self.n_worlds if total_worlds is None else int(total_worlds)
+        if int(first_world) < 0 or int(first_world) + self.n_worlds > total:
+            raise ValueError(f"worlds {first_world}..{int(first_world) + self.n_worlds - 1} do not lie inside a population of {total}")
+        m = None
+        if mask is not None:
+            m = t.as_tensor(mask, device=self.sim.device)
+            if tuple(m.shape) != (self.n_worlds,):
+                raise ValueError(f"Expected a reset mask of shape ({self.n_worlds},), but got {tuple(m.shape)}")
+            m = (m != 0).to(t.uint8).contiguous()
+        _native.check(_native.lib().nmf_cpg_reset(h, None if m is None else m.data_ptr(), int(first_world), total, self.sim._stream()))
+
+    def advance(self, n_steps: int):
+        """Advance every world by ``n_steps`` (1..table_steps) in one launch and write rows ``0 .. n_steps - 1`` of the
+        controller's table; returns the table ``(n_worlds, table_steps, n_act)`` (a view: the next call overwrites it)."""
+        h = self._handle()
+        n = int(n_steps)
+        if not 1 <= n <= self.table_steps:
+            raise ValueError(f"n_steps must be in 1..{self.table_steps} (table_steps), got {n_steps}")
+        _native.check(_native.lib().nmf_cpg_advance(h, n, self.table.data_ptr(), self.table_steps, self.sim._stream()))
+        return self.table
+
+    def step(self, n_steps: int, record_every: int | None = None):
+        """One control tick: :meth:`advance`, then ``sim.step_replay`` over the rows just written (returns its observation
+        ring when ``record_every`` is given)."""
+        table = self.advance(n_steps)
+        return self.sim.step_replay(table, self.act_ids, 0, int(n_steps), record_every)

@@ -20,6 +20,7 @@
 #include "nmf_eyes.hip"
 #include "nmf_camera.hip"
 #include "nmf_replay.hip"
+#include "nmf_cpg.hip"
 
 namespace {
 
@@ -1306,6 +1307,123 @@ extern "C" int nmf_eye_render(nmf_batch* b, const nmf_eye_params* p, const float
     L.push_back(plan);
   }
   return nmf_eye_render_planned(b, p, plan, spheres_dev, capsule_seg_dev, capsule_geom_dev, frames_out_dev, omm_out_dev, stream);
+}
+
+// ---- closed-loop tripod CPG (nmf_cpg.hip) ----
+// The controller's shared tables (own device copies) and its per-world state.
+struct nmf_cpg {
+  int device = 0, n_worlds = 0, table_steps = 0;
+  nmf::CpgArgs args{};
+  float* cycle = nullptr; float* mean = nullptr; int* leg_of_col = nullptr; uint8_t* stance = nullptr;
+  double* phase = nullptr; float* mag = nullptr; double* mag_acc = nullptr; float* drive = nullptr;   // mag_acc: the magnitudes' float64 sums
+  std::vector<void*> allocs;
+};
+
+extern "C" size_t nmf_cpg_params_size(void) { return sizeof(nmf_cpg_params); }
+
+extern "C" void nmf_cpg_destroy(nmf_cpg* C) {
+  if (!C) return;
+  DeviceGuard guard(C->device);
+  for (void* q : C->allocs) (void)hipFree(q);      // (hipFree waits for the kernels that read them)
+  delete C;
+}
+
+extern "C" int nmf_cpg_reset(nmf_cpg* C, const uint8_t* mask_dev, int first_world, int total_worlds, void* stream) {
+  if (!C) return fail("nmf_cpg_reset: null controller");
+  if (first_world < 0 || total_worlds < 1 || (int64_t)first_world + C->n_worlds > (int64_t)total_worlds)
+    return fail("nmf_cpg_reset: the controller's worlds [first_world, first_world + n_worlds) must lie inside [0, total_worlds)");
+  DEVICE_GUARD(C);
+  hipLaunchKernelGGL(nmf::nmf_cpg_reset_kernel, dim3((unsigned)((6 * C->n_worlds + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     C->n_worlds, mask_dev, first_world, total_worlds, C->phase, C->mag, C->mag_acc, C->drive);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+static int fill_cpg(nmf_cpg* C, const nmf_cpg_params* p, const float* cycle, const int32_t* leg_of_col, const uint8_t* stance) {
+  if (p->n_pos < 1 || p->n_pos > 4096) return fail("nmf_cpg_create: need 1 <= n_pos <= 4096 position columns");
+  if (p->n_bins < 2 || p->n_bins > (1 << 20)) return fail("nmf_cpg_create: need 2 <= n_bins <= 2^20 phase bins");
+  if (p->table_steps < 1) return fail("nmf_cpg_create: table_steps must be at least 1");
+  if (!(p->timestep > 0.0) || !std::isfinite(p->frequency) || !std::isfinite(p->coupling) || !std::isfinite(p->convergence))
+    return fail("nmf_cpg_create: the timestep must be positive, frequency / coupling / convergence finite");
+  if (!cycle || !leg_of_col) return fail("nmf_cpg_create: cycle and leg_of_col are required");
+  for (int c = 0; c < p->n_pos; ++c)
+    if (leg_of_col[c] < 0 || leg_of_col[c] > 5) return fail("nmf_cpg_create: leg_of_col[" + std::to_string(c) + "] is outside 0..5");
+  nmf::CpgArgs& A = C->args;
+  A.n_worlds = C->n_worlds; A.n_pos = p->n_pos; A.n_act = p->n_pos + (stance ? 6 : 0); A.n_bins = p->n_bins;
+  A.frequency = p->frequency; A.timestep = p->timestep;
+  A.coupling = p->coupling; A.convergence = p->convergence; A.adhesion_on = p->adhesion_on; A.adhesion_off = p->adhesion_off;
+  C->table_steps = p->table_steps;
+  std::vector<float> mean((size_t)p->n_pos);
+  for (int c = 0; c < p->n_pos; ++c) {
+    double sum = 0.0;
+    for (int i = 0; i < p->n_bins; ++i) sum += (double)cycle[(size_t)i * p->n_pos + c];
+    mean[(size_t)c] = (float)(sum / (double)p->n_bins);
+  }
+  auto alloc = [&](const void* src, size_t bytes) -> void* {
+    void* q = nullptr;
+    if (hipMalloc(&q, std::max(bytes, (size_t)16)) != hipSuccess) return nullptr;
+    C->allocs.push_back(q);
+    if (src && hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    return q;
+  };
+  const size_t n = (size_t)C->n_worlds;
+  C->cycle = (float*)alloc(cycle, sizeof(float) * (size_t)p->n_bins * (size_t)p->n_pos);
+  C->mean = (float*)alloc(mean.data(), sizeof(float) * mean.size());
+  C->leg_of_col = (int*)alloc(leg_of_col, sizeof(int) * (size_t)p->n_pos);
+  C->stance = (uint8_t*)alloc(stance, stance ? (size_t)p->n_bins * 6 : 0);
+  C->phase = (double*)alloc(nullptr, sizeof(double) * 6 * n);
+  C->mag = (float*)alloc(nullptr, sizeof(float) * 6 * n);
+  C->mag_acc = (double*)alloc(nullptr, sizeof(double) * 6 * n);
+  C->drive = (float*)alloc(nullptr, sizeof(float) * 2 * n);
+  if (!C->cycle || !C->mean || !C->leg_of_col || !C->stance || !C->phase || !C->mag || !C->mag_acc || !C->drive)
+    return fail("nmf_cpg_create: out of device memory");
+  if (nmf_cpg_reset(C, nullptr, 0, C->n_worlds, nullptr) != 0) return -1;
+  HIP_OK(hipDeviceSynchronize());
+  return 0;
+}
+
+extern "C" nmf_cpg* nmf_cpg_create(nmf_batch* b, const nmf_cpg_params* p, const float* cycle, const int32_t* leg_of_col, const uint8_t* stance) {
+  if (!b || !p) { fail("nmf_cpg_create: null batch / params"); return nullptr; }
+  DeviceGuard guard(b->device);
+  if (guard.err != hipSuccess) { fail(std::string("hipSetDevice: ") + hipGetErrorString(guard.err)); return nullptr; }
+  nmf_cpg* C = new nmf_cpg();
+  C->device = b->device; C->n_worlds = b->n_worlds;
+  if (fill_cpg(C, p, cycle, leg_of_col, stance) != 0) {
+    const std::string keep = g_err;
+    nmf_cpg_destroy(C);
+    g_err = keep;
+    return nullptr;
+  }
+  return C;
+}
+
+extern "C" void* nmf_cpg_field_ptr(nmf_cpg* C, int which, int32_t* width) {
+  if (!C) { fail("nmf_cpg_field_ptr: null controller"); return nullptr; }
+  void* ptr[3] = {C->phase, C->mag, C->drive};
+  const int32_t w[3] = {6, 6, 2};
+  if (which < 0 || which > 2) { fail("nmf_cpg_field_ptr: no such field"); return nullptr; }
+  if (width) *width = w[which];
+  return ptr[which];
+}
+
+// Pure stream-ordered work: argument checks on the host, one kernel launch.
+extern "C" int nmf_cpg_advance(nmf_cpg* C, int n_steps, float* table_dev, int table_steps, void* stream) {
+  if (!C) return fail("nmf_cpg_advance: null controller");
+  if (!table_dev) return fail("nmf_cpg_advance: null table");
+  if (table_steps != C->table_steps) return fail("nmf_cpg_advance: the controller was made for tables of " + std::to_string(C->table_steps) + " steps, got " + std::to_string(table_steps));
+  if (n_steps < 1 || n_steps > table_steps) return fail("nmf_cpg_advance: n_steps must be in 1.." + std::to_string(table_steps) + ", got " + std::to_string(n_steps));
+  DEVICE_GUARD(C);
+  // the table must live on the controller's device (a pointer query is no stream work, but a capture is left alone)
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing((hipStream_t)stream, &capturing) == hipSuccess && capturing == hipStreamCaptureStatusNone) {
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, table_dev) != hipSuccess) { (void)hipGetLastError(); return fail("nmf_cpg_advance: the table is not device memory"); }
+    if (at.device != C->device) return fail("nmf_cpg_advance: the controller was made for device " + std::to_string(C->device) + ", the table is on device " + std::to_string(at.device));
+  }
+  hipLaunchKernelGGL(nmf::nmf_cpg_advance_kernel, dim3((unsigned)((C->n_worlds + nmf::kCpgWorlds - 1) / nmf::kCpgWorlds)), dim3(nmf::kCpgThreads), 0,
+                     (hipStream_t)stream, C->args, C->cycle, C->mean, C->leg_of_col, C->stance, C->drive, C->phase, C->mag, C->mag_acc, table_dev, table_steps, n_steps);
+  HIP_OK(hipGetLastError());
+  return 0;
 }
 
 extern "C" int nmf_odor_intensity(nmf_batch* b, const int32_t* sensor_seg_dev, const float* sensor_rel_dev, int n_sensors,

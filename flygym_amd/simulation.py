@@ -606,7 +606,7 @@ class MultiFlyHIPSimulation(HIPSimulation):
     def mj_data(self): self._one_batch_only("mj_data")
 
 
-def _tensor_from_ptr(torch, ptr: int, shape, device):
+def _tensor_from_ptr(torch, ptr: int, shape, device, typestr: str = "<f4"):
     """Wrap a raw device pointer as a torch tensor without copying."""
     n = int(np.prod(shape))
 
@@ -615,7 +615,7 @@ def _tensor_from_ptr(torch, ptr: int, shape, device):
 
     h = _Holder()
     h.__cuda_array_interface__ = {
-        "shape": (max(n, 1),), "typestr": "<f4", "data": (int(ptr), False), "version": 3, "strides": None,
+        "shape": (max(n, 1),), "typestr": typestr, "data": (int(ptr), False), "version": 3, "strides": None,
     }
     t = torch.as_tensor(h, device=device)
     return t[:n].reshape(shape)

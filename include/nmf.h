@@ -26,6 +26,7 @@ typedef struct nmf_model nmf_model;
 typedef struct nmf_batch nmf_batch;
 typedef struct nmf_eye_plan nmf_eye_plan;
 typedef struct nmf_camera_plan nmf_camera_plan;
+typedef struct nmf_cpg nmf_cpg;
 
 /* Per-world fields addressable through nmf_field_ptr / nmf_gather_* */
 enum nmf_field {
@@ -331,6 +332,60 @@ void nmf_camera_plan_destroy(nmf_camera_plan* plan);
  * [n_spheres][4], or [n_worlds][n_spheres][4] with spheres_per_world = 1.  frames_out_dev: uint8
  * [n_selected][n_cameras][height][width][3], 16-byte aligned. */
 int nmf_camera_render(nmf_batch* batch, const nmf_camera_plan* plan, const float* spheres_dev, uint8_t* frames_out_dev, void* stream);
+
+/* Closed-loop steerable tripod CPG with its state on the device (flygym_amd.controllers.TurningCPG; csrc/nmf_cpg.hip).  No
+ * reference counterpart: the snapshot has no CPG (flygym 2.0.1 dropped flygym 1.x's controllers), so this is build-defined
+ * (specification tests/cpg_spec.py).  Per world six coupled phase oscillators, legs in the order lf lm lh
+ * rf rm rh (side = leg / 3, tripod phase bias b = pi * (leg & 1)): phase theta in cycles in [0, 1) (float64), magnitude r
+ * (float32), and an input drive d = (d_left, d_right) (float32).  One step at dt = timestep writes one table row from the state
+ * BEFORE its update, and every right-hand side uses the old state:
+ *   x = theta_l n_bins, i0 = floor(x) mod n_bins, f = x - floor(x), c = (1 - f) cycle[i0][col] + f cycle[(i0 + 1) mod n_bins][col]
+ *   row[col] = c + (r_l - 1) (c - mean[col])   (l = leg_of_col[col]; mean = the cycle's mean over its bins; r = 1: c itself)
+ *   row[n_pos + l] = stance[i0][l] ? adhesion_on : adhesion_off        (the six optional columns)
+ *   theta_l <- (theta_l + dt (frequency sign(d_side) + (1 / 2 pi) sum_{j != l} r_j coupling sin(2 pi (theta_j - theta_l) - (b_j - b_l)))) mod 1
+ *   r_l     <- r_l + dt convergence (|d_side| - r_l)                   (sign(0) = 0: that side holds its phase)
+ * The phase, x and the phase increment are float64, everything else float32; the magnitudes' Euler sums are kept in float64
+ * beside the float32 array the formulas read (a magnitude the caller writes takes effect at the next launch). */
+typedef struct nmf_cpg_params {
+  int32_t n_pos;                /* position-target columns of a row (1..4096)                                            */
+  int32_t n_bins;               /* phase bins of the step cycle (>= 2)                                                   */
+  double frequency;             /* Hz at |drive| > 0                                                                     */
+  double timestep;              /* seconds per step (the batch's physics timestep)                                       */
+  float coupling;               /* weight w of every pair                                                                */
+  float convergence;            /* rate a of the magnitudes                                                              */
+  float adhesion_on, adhesion_off;   /* values of the adhesion columns in stance / swing (used with stance bins only)   */
+  int32_t table_steps;          /* rows per world of the tables nmf_cpg_advance will be given (>= 1)                     */
+} nmf_cpg_params;
+
+/* sizeof(nmf_cpg_params) as this library was compiled (as nmf_eye_params_size). */
+size_t nmf_cpg_params_size(void);
+
+/* An explicit handle for the worlds of `batch`, on its device: takes HOST arrays — cycle[n_bins][n_pos] float32,
+ * leg_of_col[n_pos] (each in 0..5), stance[n_bins][6] uint8 or NULL (NULL: rows of n_pos columns; else n_pos + 6) — validates
+ * them, owns device copies and the state arrays, and resets every world (nmf_cpg_reset with first_world 0 of n_worlds).  NOT
+ * stream-ordered (allocations, synchronous uploads); must not be called inside a stream capture.  NULL on error
+ * (nmf_last_error): n_bins < 2, a leg_of_col outside 0..5, ... */
+nmf_cpg* nmf_cpg_create(nmf_batch* batch, const nmf_cpg_params* params, const float* cycle, const int32_t* leg_of_col,
+                        const uint8_t* stance);
+void nmf_cpg_destroy(nmf_cpg* cpg);
+
+/* The worlds with mask_dev[w] != 0 (uint8 per world, device memory; NULL: all) get theta_l = ((first_world + w) / total_worlds +
+ * b_l / 2 pi) mod 1, r = 1, drive = (1, 1): the tripod, world by world one gait cycle apart — first_world / total_worlds place
+ * a shard inside a larger (multi-GPU) population, as TripodCPG.targets does.  The others keep their state.  Stream-ordered. */
+int nmf_cpg_reset(nmf_cpg* cpg, const uint8_t* mask_dev, int first_world, int total_worlds, void* stream);
+
+/* Device pointer + row width of a per-world array of the controller (zero-copy views; writable between launches). */
+#define NMF_CPG_PHASE 0           /* [6] float64, cycles in [0, 1) */
+#define NMF_CPG_MAGNITUDE 1       /* [6] float32                   */
+#define NMF_CPG_DRIVE 2           /* [2] float32 (left, right)     */
+void* nmf_cpg_field_ptr(nmf_cpg* cpg, int which, int32_t* width);
+
+/* Advance every world by n_steps and write table_dev[w][s][0 .. n_act) for s < n_steps (float32 [n_worlds][table_steps][n_act],
+ * n_act = n_pos or n_pos + 6: the table of nmf_step_replay / nmf_step_record with start = 0); rows n_steps .. table_steps - 1
+ * are not touched.  The drive is read when the launch starts.  Argument checks and ONE kernel launch on `stream`: no allocation,
+ * no host synchronisation, hipGraph-capturable.  Refused: a null table, table_steps other than the params', n_steps outside
+ * 1..table_steps, a table on another device than the controller's (checked outside stream captures). */
+int nmf_cpg_advance(nmf_cpg* cpg, int n_steps, float* table_dev, int table_steps, void* stream);
 
 /* Odor intensity at n_sensors points rigidly attached to named segments (sensor_seg = index into the
  * batch's segment order, sensor_rel = offset in the segment frame): out[w][d][k] = sum_s peak[s][d] / dist^2.
