@@ -169,6 +169,9 @@ def lib():
             "nmf_cpg_reset": (ci, [vp, vp, ci, ci, vp]),
             "nmf_cpg_field_ptr": (vp, [vp, ci, ctypes.POINTER(ctypes.c_int32)]),
             "nmf_cpg_advance": (ci, [vp, ci, vp, ci, vp]),
+            "nmf_cpg_hybrid_params_size": (ctypes.c_size_t, []),
+            "nmf_cpg_hybrid_enable": (ci, [vp, vp, vp, vp, ci, vp]),
+            "nmf_cpg_advance_hybrid": (ci, [vp, ci, vp, ci, vp]),
             "nmf_odor_intensity": (ci, [vp, vp, vp, ci, vp, vp, ci, ci, vp, vp]),
             "nmf_replay_resample": (ci, [vp, ci, ci, ctypes.c_double, ctypes.c_double, vp, ci, ci, vp, vp]),
         }

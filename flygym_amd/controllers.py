@@ -1,5 +1,6 @@
-"""Controllers that produce position-actuator targets for the batched engine: the open-loop ``TripodCPG`` table builder and
-the closed-loop, steerable ``TurningCPG`` whose state lives on the GPU (at the end of this docstring).
+"""Controllers that produce position-actuator targets for the batched engine: the open-loop ``TripodCPG`` table builder, the
+closed-loop, steerable ``TurningCPG`` whose state lives on the GPU, and ``HybridTurningCPG``, which adds flygym 1.x's two sensory
+rules (retraction, stumbling) to it (both at the end of this docstring).
 
 ``TripodCPG`` is the "position-actuated CPG tripod gait" of BASELINE config 2.  The reference snapshot has
 no CPG (flygym 2.0.1 dropped flygym 1.x's controllers), so this one is build-defined:
@@ -24,6 +25,12 @@ which the claw is near its lowest point (forward kinematics of the cycle in the 
 turning controller): six coupled phase oscillators per world with a phase (cycles, float64) and a magnitude each, and a per-world
 drive ``(d_left, d_right)`` — ``|d|`` is the magnitude a side's legs converge to, ``sign(d)`` the direction its phases run in.
 With the unit drive it reproduces ``TripodCPG.targets``; a weaker side shortens that side's strides and the fly turns towards it.
+
+``HybridTurningCPG`` is that CPG plus the rule half of flygym 1.x's hybrid controller (specification ``tests/hybrid_spec.py``;
+build-defined and pinned by nothing: the rules are this project's statement of them, the default constants flygym 1.x's as
+remembered): a leg that hangs much lower than the others (it stepped into a gap) and a leg that is pushed backwards
+while it swings (it hit a wall) are lifted by a correction added to their targets.  The rules read the batch's pose and contact
+sensors once per launch; the oscillators are not changed by them.
 """
 
 from __future__ import annotations
@@ -36,7 +43,7 @@ from . import _native
 from .anatomy import LEGS, JointDOF
 from .replay import MotionSnippet
 
-__all__ = ["TripodCPG", "TurningCPG"]
+__all__ = ["TripodCPG", "TurningCPG", "HybridTurningCPG"]
 
 TRIPOD_PHASE_BIAS = {"lf": 0.0, "rm": 0.0, "lh": 0.0, "rf": np.pi, "lm": np.pi, "rh": np.pi}
 
@@ -170,6 +177,9 @@ class TripodCPG:
             frac = (x - torch.floor(x)).to(torch.float32)
             out[w0:w0 + len(w)] = (1 - frac) * cyc[i0, cols] + frac * cyc[(i0 + 1) % self.n_bins, cols]
         return out
+
+
+STUMBLING_DEFAULT = 5.2          # force units: 1.25 x the most negative push of a swinging leg in flat walking (profiles/hybrid_cpg.txt)
 
 
 class _CpgParams(ctypes.Structure):
@@ -319,3 +329,125 @@ class TurningCPG(TripodCPG):
         ring when ``record_every`` is given)."""
         table = self.advance(n_steps)
         return self.sim.step_replay(table, self.act_ids, 0, int(n_steps), record_every)
+
+
+class _CpgHybridParams(ctypes.Structure):
+    """``nmf_cpg_hybrid_params`` of include/nmf.h."""
+
+    _fields_ = [("retraction_threshold", ctypes.c_float), ("stumbling_force_threshold", ctypes.c_float),
+                ("retraction_up", ctypes.c_float), ("retraction_down", ctypes.c_float), ("stumbling_up", ctypes.c_float),
+                ("stumbling_down", ctypes.c_float), ("max_correction", ctypes.c_float)]
+
+
+# Radians per unit of net correction over the seven leg dofs in the walking clip's order (coxa pitch, roll, yaw, femur pitch, roll,
+# tibia pitch, tarsus pitch), by leg position: flygym 1.x's vectors as remembered.  The clip's angles are anatomical (a right leg
+# mirrors its left one), so one vector serves both sides.
+CORRECTION_VECTORS = {"f": (-0.03, 0.0, 0.0, -0.03, 0.0, 0.03, 0.03), "m": (-0.015, 0.001, 0.025, -0.02, 0.0, -0.02, 0.0),
+                      "h": (0.0, 0.0, 0.0, -0.02, 0.0, 0.01, -0.02)}
+
+
+class HybridTurningCPG(TurningCPG):
+    """:class:`TurningCPG` plus the retraction and stumbling rules, advanced on the GPU (``nmf_cpg_advance_hybrid``).
+
+    Decided once per launch, from the batch's ``seg_xpos`` / ``seg_xquat`` / ``sensordata`` as they stand when it starts (the last
+    step of the previous tick; with ``advance(1)`` this is flygym 1.x's per-step rule)::
+
+        h_l = z(root segment) - z(origin of {leg}_tarsus5);  L = argmax h (ties: the lowest index);  h3 = the third largest h
+        retract[L] = h_L > h3 + retraction_threshold                                   (at most one leg per world)
+        stumble[l] = leg l swings (the complement of stance_bins at its phase) and found_l > 0 and F_l . xhat < -stumbling_force_threshold
+
+    with ``xhat`` the root segment's x axis and ``F_l`` the leg's net sensor force, both in the world frame.  Per step, the flags
+    held for the launch and the row computed from the state before its update::
+
+        net_l = rho_l > 0 ? rho_l : sigma_l
+        target[col] = target of the CPG + net_l corr[col]          adhesion[l] = off while net_l > 0
+        rho_l   <- retract[l] ? min(rho_l + dt up_r, max_correction)   : max(rho_l - dt down_r, 0)
+        sigma_l <- stumble[l] ? min(sigma_l + dt up_s, max_correction) : max(sigma_l - dt down_s, 0)
+
+    Args (beside :class:`TurningCPG`'s; the defaults are flygym 1.x's as remembered, the two thresholds measured on this model,
+    ``profiles/hybrid_cpg.txt``):
+        retraction_threshold: in the model's length unit.
+        stumbling_force_threshold: in the contact sensors' force unit.
+        retraction_rates, stumbling_rates: ``(up, down)`` per second.
+        max_correction: the cap of ``rho`` and ``sigma``.
+        correction_vectors: ``{"f": ..., "m": ..., "h": ...}``, seven values each over the leg dofs in the walking clip's order;
+            columns of dofs outside the clip get 0.
+
+    ``retraction`` and ``stumbling`` ``(n, 6)`` float32 and ``rule_flags`` ``(n, 6)`` uint8 (bit 0 retract, bit 1 stumble: the last
+    launch's decision) are zero-copy views; :meth:`reset` clears them for the masked worlds.
+    """
+
+    def __init__(self, sim, fly_name: str, *, retraction_threshold: float = 0.05, stumbling_force_threshold: float = STUMBLING_DEFAULT,
+                 retraction_rates=(800.0, 700.0), stumbling_rates=(2200.0, 1800.0), max_correction: float = 80.0,
+                 correction_vectors=None, **kw):
+        super().__init__(sim, fly_name, **kw)
+        try:
+            self._enable(retraction_threshold, stumbling_force_threshold, retraction_rates, stumbling_rates, max_correction,
+                         correction_vectors)
+        except Exception:
+            self.close()
+            raise
+
+    @staticmethod
+    def correction_row(actuated_dofs, correction_vectors=None) -> np.ndarray:
+        """``corr[n_pos]`` float32 for the columns ``actuated_dofs``: the vector of the leg's position at the dof's place in the
+        walking clip's order, 0 for a dof the clip does not have."""
+        vectors = dict(CORRECTION_VECTORS, **(correction_vectors or {}))
+        clip_dofs = MotionSnippet().dofs_per_leg
+        for key, vec in vectors.items():
+            if key not in CORRECTION_VECTORS or len(vec) != len(clip_dofs):
+                raise ValueError(f"correction_vectors takes {len(clip_dofs)} values for each of 'f', 'm', 'h', got {key!r}: {vec!r}")
+        corr = np.zeros(len(actuated_dofs), dtype=np.float32)
+        for c, d in enumerate(actuated_dofs):
+            key = (d.parent.link, d.child.link, d.axis.value)
+            if key in clip_dofs:
+                corr[c] = vectors[d.child.pos[1]][clip_dofs.index(key)]
+        return corr
+
+    def _enable(self, retraction_threshold, stumbling_force_threshold, retraction_rates, stumbling_rates, max_correction,
+                correction_vectors):
+        sim, lib = self.sim, _native.lib()
+        fly = sim.world.fly_lookup[self.fly_name]
+        if len(retraction_rates) != 2 or len(stumbling_rates) != 2:
+            raise ValueError("retraction_rates and stumbling_rates are (up, down) pairs")
+        self.retraction_threshold, self.stumbling_force_threshold = float(retraction_threshold), float(stumbling_force_threshold)
+        self.retraction_rates = (float(retraction_rates[0]), float(retraction_rates[1]))
+        self.stumbling_rates = (float(stumbling_rates[0]), float(stumbling_rates[1]))
+        self.max_correction = float(max_correction)
+        self.corr = self.correction_row(self.actuated_dofs, correction_vectors)
+        # swing: the complement of the stance bins, whether or not the table has adhesion columns
+        stance = self.stance if self.stance is not None else self.stance_bins(sim.model, fly)
+        self.swing = np.ascontiguousarray(~np.asarray(stance, dtype=bool), dtype=np.uint8)
+        segs = [s.name for s in fly.get_bodysegs_order()]
+        self.root_seg = segs.index(fly.root_segment.name)
+        self.tip_seg = np.array([segs.index(f"{leg}_tarsus5") for leg in LEGS], dtype=np.int32)
+        if ctypes.sizeof(_CpgHybridParams) != lib.nmf_cpg_hybrid_params_size():
+            raise _native.NativeError("nmf_cpg_hybrid_params layout mismatch between controllers.py and libnmf_hip.so")
+        self._hybrid_params = _CpgHybridParams(self.retraction_threshold, self.stumbling_force_threshold, *self.retraction_rates,
+                                               *self.stumbling_rates, self.max_correction)
+        _native.check(lib.nmf_cpg_hybrid_enable(self._h, ctypes.byref(self._hybrid_params), self.corr.ctypes.data,
+                                                self.swing.ctypes.data, self.root_seg, self.tip_seg.ctypes.data))
+        from .simulation import _tensor_from_ptr
+
+        views = []
+        for which, typestr in ((3, "<f4"), (4, "<f4"), (5, "|u1")):
+            width = ctypes.c_int32(0)
+            ptr = lib.nmf_cpg_field_ptr(self._h, which, ctypes.byref(width))
+            if not ptr:
+                raise _native.NativeError(lib.nmf_last_error().decode())
+            views.append(_tensor_from_ptr(sim._torch, ptr, (self.n_worlds, width.value), sim.device, typestr))
+        self.retraction, self.stumbling, self.rule_flags = views
+
+    def close(self) -> None:
+        super().close()
+        self.retraction = self.stumbling = self.rule_flags = None
+
+    def advance(self, n_steps: int):
+        """:meth:`TurningCPG.advance` with the rules: the launch decides from the batch's current pose and sensor outputs, writes
+        :attr:`rule_flags` and advances :attr:`retraction` / :attr:`stumbling` with the oscillators."""
+        h = self._handle()
+        n = int(n_steps)
+        if not 1 <= n <= self.table_steps:
+            raise ValueError(f"n_steps must be in 1..{self.table_steps} (table_steps), got {n_steps}")
+        _native.check(_native.lib().nmf_cpg_advance_hybrid(h, n, self.table.data_ptr(), self.table_steps, self.sim._stream()))
+        return self.table

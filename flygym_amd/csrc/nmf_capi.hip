@@ -1316,6 +1316,11 @@ struct nmf_cpg {
   nmf::CpgArgs args{};
   float* cycle = nullptr; float* mean = nullptr; int* leg_of_col = nullptr; uint8_t* stance = nullptr;
   double* phase = nullptr; float* mag = nullptr; double* mag_acc = nullptr; float* drive = nullptr;   // mag_acc: the magnitudes' float64 sums
+  // the hybrid rules (nmf_cpg_hybrid_enable): the batch whose pose / sensor outputs the decision reads, and the rules' state
+  const nmf_batch* batch = nullptr;
+  bool hybrid = false;
+  nmf::CpgHybridArgs hargs{};
+  nmf::CpgHybridPtrs hptrs{};
   std::vector<void*> allocs;
 };
 
@@ -1336,6 +1341,11 @@ extern "C" int nmf_cpg_reset(nmf_cpg* C, const uint8_t* mask_dev, int first_worl
   hipLaunchKernelGGL(nmf::nmf_cpg_reset_kernel, dim3((unsigned)((6 * C->n_worlds + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      C->n_worlds, mask_dev, first_world, total_worlds, C->phase, C->mag, C->mag_acc, C->drive);
   HIP_OK(hipGetLastError());
+  if (C->hybrid) {
+    hipLaunchKernelGGL(nmf::nmf_cpg_hybrid_reset_kernel, dim3((unsigned)((6 * C->n_worlds + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       C->n_worlds, mask_dev, C->hptrs.retraction, C->hptrs.stumbling, C->hptrs.flags);
+    HIP_OK(hipGetLastError());
+  }
   return 0;
 }
 
@@ -1387,7 +1397,7 @@ extern "C" nmf_cpg* nmf_cpg_create(nmf_batch* b, const nmf_cpg_params* p, const 
   DeviceGuard guard(b->device);
   if (guard.err != hipSuccess) { fail(std::string("hipSetDevice: ") + hipGetErrorString(guard.err)); return nullptr; }
   nmf_cpg* C = new nmf_cpg();
-  C->device = b->device; C->n_worlds = b->n_worlds;
+  C->device = b->device; C->n_worlds = b->n_worlds; C->batch = b;
   if (fill_cpg(C, p, cycle, leg_of_col, stance) != 0) {
     const std::string keep = g_err;
     nmf_cpg_destroy(C);
@@ -1399,29 +1409,105 @@ extern "C" nmf_cpg* nmf_cpg_create(nmf_batch* b, const nmf_cpg_params* p, const 
 
 extern "C" void* nmf_cpg_field_ptr(nmf_cpg* C, int which, int32_t* width) {
   if (!C) { fail("nmf_cpg_field_ptr: null controller"); return nullptr; }
-  void* ptr[3] = {C->phase, C->mag, C->drive};
-  const int32_t w[3] = {6, 6, 2};
-  if (which < 0 || which > 2) { fail("nmf_cpg_field_ptr: no such field"); return nullptr; }
+  void* ptr[6] = {C->phase, C->mag, C->drive, C->hptrs.retraction, C->hptrs.stumbling, C->hptrs.flags};
+  const int32_t w[6] = {6, 6, 2, 6, 6, 6};
+  if (which < 0 || which > 5) { fail("nmf_cpg_field_ptr: no such field"); return nullptr; }
+  if (which > 2 && !C->hybrid) { fail("nmf_cpg_field_ptr: the hybrid rules are not enabled (nmf_cpg_hybrid_enable)"); return nullptr; }
   if (width) *width = w[which];
   return ptr[which];
 }
 
 // Pure stream-ordered work: argument checks on the host, one kernel launch.
-extern "C" int nmf_cpg_advance(nmf_cpg* C, int n_steps, float* table_dev, int table_steps, void* stream) {
-  if (!C) return fail("nmf_cpg_advance: null controller");
-  if (!table_dev) return fail("nmf_cpg_advance: null table");
-  if (table_steps != C->table_steps) return fail("nmf_cpg_advance: the controller was made for tables of " + std::to_string(C->table_steps) + " steps, got " + std::to_string(table_steps));
-  if (n_steps < 1 || n_steps > table_steps) return fail("nmf_cpg_advance: n_steps must be in 1.." + std::to_string(table_steps) + ", got " + std::to_string(n_steps));
+static int cpg_advance_checks(const char* who, nmf_cpg* C, int n_steps, float* table_dev, int table_steps, void* stream) {
+  const std::string w(who);
+  if (!C) return fail(w + ": null controller");
+  if (!table_dev) return fail(w + ": null table");
+  if (table_steps != C->table_steps) return fail(w + ": the controller was made for tables of " + std::to_string(C->table_steps) + " steps, got " + std::to_string(table_steps));
+  if (n_steps < 1 || n_steps > table_steps) return fail(w + ": n_steps must be in 1.." + std::to_string(table_steps) + ", got " + std::to_string(n_steps));
   DEVICE_GUARD(C);
   // the table must live on the controller's device (a pointer query is no stream work, but a capture is left alone)
   hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing((hipStream_t)stream, &capturing) == hipSuccess && capturing == hipStreamCaptureStatusNone) {
     hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, table_dev) != hipSuccess) { (void)hipGetLastError(); return fail("nmf_cpg_advance: the table is not device memory"); }
-    if (at.device != C->device) return fail("nmf_cpg_advance: the controller was made for device " + std::to_string(C->device) + ", the table is on device " + std::to_string(at.device));
+    if (hipPointerGetAttributes(&at, table_dev) != hipSuccess) { (void)hipGetLastError(); return fail(w + ": the table is not device memory"); }
+    if (at.device != C->device) return fail(w + ": the controller was made for device " + std::to_string(C->device) + ", the table is on device " + std::to_string(at.device));
   }
+  return 0;
+}
+
+extern "C" int nmf_cpg_advance(nmf_cpg* C, int n_steps, float* table_dev, int table_steps, void* stream) {
+  if (cpg_advance_checks("nmf_cpg_advance", C, n_steps, table_dev, table_steps, stream) != 0) return -1;
+  DEVICE_GUARD(C);
   hipLaunchKernelGGL(nmf::nmf_cpg_advance_kernel, dim3((unsigned)((C->n_worlds + nmf::kCpgWorlds - 1) / nmf::kCpgWorlds)), dim3(nmf::kCpgThreads), 0,
                      (hipStream_t)stream, C->args, C->cycle, C->mean, C->leg_of_col, C->stance, C->drive, C->phase, C->mag, C->mag_acc, table_dev, table_steps, n_steps);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// ---- the hybrid rules of the CPG (retraction, stumbling) ----
+extern "C" size_t nmf_cpg_hybrid_params_size(void) { return sizeof(nmf_cpg_hybrid_params); }
+
+extern "C" int nmf_cpg_hybrid_enable(nmf_cpg* C, const nmf_cpg_hybrid_params* p, const float* corr, const uint8_t* swing, int root_seg,
+                                     const int32_t tip_seg[6]) {
+  if (!C) return fail("nmf_cpg_hybrid_enable: null controller");
+  if (!p || !corr || !swing || !tip_seg) return fail("nmf_cpg_hybrid_enable: params, corr, swing and tip_seg are required");
+  if (C->hybrid) return fail("nmf_cpg_hybrid_enable: the hybrid rules of this controller are already enabled");
+  const nmf_batch* b = C->batch;
+  if (b->model->nsensor == 0 || !b->st.sensordata) return fail("nmf_cpg_hybrid_enable: the batch's model has no leg sensors (nsensor == 0)");
+  if (b->widths[NMF_SENSORDATA] != 96)
+    return fail("nmf_cpg_hybrid_enable: the batch's sensordata is " + std::to_string(b->widths[NMF_SENSORDATA]) + " wide, the rules read six leg sensors of 16 values");
+  const int nseg = b->model->nseg;
+  if (root_seg < 0 || root_seg >= nseg) return fail("nmf_cpg_hybrid_enable: root_seg " + std::to_string(root_seg) + " is outside the batch's " + std::to_string(nseg) + " segments");
+  for (int l = 0; l < 6; ++l)
+    if (tip_seg[l] < 0 || tip_seg[l] >= nseg) return fail("nmf_cpg_hybrid_enable: tip_seg[" + std::to_string(l) + "] = " + std::to_string(tip_seg[l]) + " is outside the batch's " + std::to_string(nseg) + " segments");
+  const float checked[7] = {p->retraction_threshold, p->stumbling_force_threshold, p->retraction_up, p->retraction_down, p->stumbling_up, p->stumbling_down, p->max_correction};
+  for (float v : checked)
+    if (!(v >= 0.f) || !std::isfinite(v)) return fail("nmf_cpg_hybrid_enable: thresholds, rates and max_correction must be finite and not negative");
+  for (int c = 0; c < C->args.n_pos; ++c)
+    if (!std::isfinite(corr[c])) return fail("nmf_cpg_hybrid_enable: corr[" + std::to_string(c) + "] is not finite");
+  DEVICE_GUARD(C);
+  nmf::CpgHybridArgs H{};
+  H.nseg = nseg; H.root_seg = root_seg; H.contact_frame = b->dm.sem_sensor_contact_frame;
+  for (int l = 0; l < 6; ++l) H.tip_seg[l] = tip_seg[l];
+  H.retraction_threshold = p->retraction_threshold; H.stumbling_force_threshold = p->stumbling_force_threshold;
+  H.up_r = (float)(C->args.timestep * (double)p->retraction_up); H.down_r = (float)(C->args.timestep * (double)p->retraction_down);
+  H.up_s = (float)(C->args.timestep * (double)p->stumbling_up); H.down_s = (float)(C->args.timestep * (double)p->stumbling_down);
+  H.cap = p->max_correction;
+  auto alloc = [&](const void* src, size_t bytes) -> void* {
+    void* q = nullptr;
+    if (hipMalloc(&q, std::max(bytes, (size_t)16)) != hipSuccess) return nullptr;
+    C->allocs.push_back(q);
+    if ((src ? hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) : hipMemset(q, 0, bytes)) != hipSuccess) return nullptr;
+    return q;
+  };
+  const size_t n = (size_t)C->n_worlds, n_allocs = C->allocs.size();
+  nmf::CpgHybridPtrs P{};
+  P.corr = (const float*)alloc(corr, sizeof(float) * (size_t)C->args.n_pos);
+  P.swing = (const uint8_t*)alloc(swing, (size_t)C->args.n_bins * 6);
+  P.retraction = (float*)alloc(nullptr, sizeof(float) * 6 * n);
+  P.stumbling = (float*)alloc(nullptr, sizeof(float) * 6 * n);
+  P.flags = (uint8_t*)alloc(nullptr, 6 * n);
+  P.seg_xpos = b->st.seg_xpos; P.seg_xquat = b->st.seg_xquat; P.sensordata = b->st.sensordata;
+  if (!P.corr || !P.swing || !P.retraction || !P.stumbling || !P.flags) {
+    (void)hipGetLastError();
+    for (size_t k = n_allocs; k < C->allocs.size(); ++k) (void)hipFree(C->allocs[k]);   // the controller stays as it was
+    C->allocs.resize(n_allocs);
+    return fail("nmf_cpg_hybrid_enable: out of device memory");
+  }
+  HIP_OK(hipDeviceSynchronize());
+  C->hargs = H;
+  C->hptrs = P;
+  C->hybrid = true;
+  return 0;
+}
+
+extern "C" int nmf_cpg_advance_hybrid(nmf_cpg* C, int n_steps, float* table_dev, int table_steps, void* stream) {
+  if (cpg_advance_checks("nmf_cpg_advance_hybrid", C, n_steps, table_dev, table_steps, stream) != 0) return -1;
+  if (!C->hybrid) return fail("nmf_cpg_advance_hybrid: the hybrid rules are not enabled (nmf_cpg_hybrid_enable)");
+  DEVICE_GUARD(C);
+  hipLaunchKernelGGL(nmf::nmf_cpg_advance_hybrid_kernel, dim3((unsigned)((C->n_worlds + nmf::kCpgWorlds - 1) / nmf::kCpgWorlds)), dim3(nmf::kCpgThreads), 0,
+                     (hipStream_t)stream, C->args, C->hargs, C->hptrs, C->cycle, C->mean, C->leg_of_col, C->stance, C->drive, C->phase, C->mag, C->mag_acc,
+                     table_dev, table_steps, n_steps);
   HIP_OK(hipGetLastError());
   return 0;
 }

@@ -378,6 +378,9 @@ int nmf_cpg_reset(nmf_cpg* cpg, const uint8_t* mask_dev, int first_world, int to
 #define NMF_CPG_PHASE 0           /* [6] float64, cycles in [0, 1) */
 #define NMF_CPG_MAGNITUDE 1       /* [6] float32                   */
 #define NMF_CPG_DRIVE 2           /* [2] float32 (left, right)     */
+#define NMF_CPG_RETRACTION 3      /* [6] float32 rho in [0, max_correction]            (after nmf_cpg_hybrid_enable) */
+#define NMF_CPG_STUMBLING 4       /* [6] float32 sigma in [0, max_correction]          (after nmf_cpg_hybrid_enable) */
+#define NMF_CPG_RULE_FLAGS 5      /* [6] uint8: bit 0 retract, bit 1 stumble, of the last hybrid launch (after enable) */
 void* nmf_cpg_field_ptr(nmf_cpg* cpg, int which, int32_t* width);
 
 /* Advance every world by n_steps and write table_dev[w][s][0 .. n_act) for s < n_steps (float32 [n_worlds][table_steps][n_act],
@@ -386,6 +389,51 @@ void* nmf_cpg_field_ptr(nmf_cpg* cpg, int which, int32_t* width);
  * no host synchronisation, hipGraph-capturable.  Refused: a null table, table_steps other than the params', n_steps outside
  * 1..table_steps, a table on another device than the controller's (checked outside stream captures). */
 int nmf_cpg_advance(nmf_cpg* cpg, int n_steps, float* table_dev, int table_steps, void* stream);
+
+/* The hybrid controller: the CPG above plus two sensory rules that lift a leg (flygym_amd.controllers.HybridTurningCPG;
+ * specification tests/hybrid_spec.py).  Build-defined and pinned by nothing, like the CPG: the rules are this project's statement
+ * of flygym 1.x's hybrid controller, the default constants are flygym 1.x's as remembered.  State per world
+ * and leg beside the CPG's: retraction rho and stumbling sigma (float32, >= 0).  The decision is taken ONCE per launch, from the
+ * batch's seg_xpos / seg_xquat / sensordata as they stand when the launch starts (the last step of the previous launch):
+ *   h_l = z(root segment) - z(tip segment of leg l); L = the leg of the largest h (ties: the lowest index); h3 = the third largest h
+ *   retract[L]  = h_L > h3 + retraction_threshold                                          (at most one leg per world)
+ *   stumble[l]  = swing[i0_l][l] and found_l > 0 and F_l . xhat < -stumbling_force_threshold
+ * i0_l: the leg's phase bin when the launch starts; xhat: the root segment's x axis in the world; F_l: the leg's net sensor force in
+ * the world frame (rebuilt from the reported normal n and tangent t1, third axis n x t1, where the model's semantics report it in
+ * the contact frame).  Per step, flags held for the launch, the row from the state before its update:
+ *   net_l = rho_l > 0 ? rho_l : sigma_l
+ *   row[col] = fl(row of the CPG + fl(net_l corr[col]))          (two float32 roundings, no fused multiply-add)
+ *   row[n_pos + l] = adhesion_off while net_l > 0                (with the six adhesion columns)
+ *   rho_l   <- retract[l] ? min(rho_l + dt retraction_up, max_correction)  : max(rho_l - dt retraction_down, 0)
+ *   sigma_l <- stumble[l] ? min(sigma_l + dt stumbling_up, max_correction) : max(sigma_l - dt stumbling_down, 0)
+ * with the four increments rounded to float32 once.  The oscillators are not modified by the rules. */
+typedef struct nmf_cpg_hybrid_params {
+  float retraction_threshold;        /* in the model's length unit (>= 0)                      */
+  float stumbling_force_threshold;   /* in the sensor's force unit (>= 0)                      */
+  float retraction_up, retraction_down;     /* rates of rho per second (>= 0)                  */
+  float stumbling_up, stumbling_down;       /* rates of sigma per second (>= 0)                */
+  float max_correction;              /* the cap of rho and sigma (>= 0)                        */
+} nmf_cpg_hybrid_params;
+
+/* sizeof(nmf_cpg_hybrid_params) as this library was compiled. */
+size_t nmf_cpg_hybrid_params_size(void);
+
+/* Switch the rules on for this controller, once: takes HOST arrays — corr[n_pos] float32 (radians per unit of net, per position
+ * column), swing[n_bins][6] uint8 — and the indices, in the batch's segment order, of the root segment and of the six legs' tip
+ * segments; validates them and allocates rho, sigma and the flags, zeroed.  NOT stream-ordered (allocations, synchronous uploads);
+ * must not be called inside a stream capture.  Refused (nmf_last_error): a second call, a segment index outside the batch's segment
+ * count, a negative or non-finite rate / cap / threshold, a non-finite corr, a batch whose model has no leg sensors (or whose
+ * sensordata is not the six leg sensors' 96 values); a refused call leaves the controller as it was.  The controller keeps
+ * pointers to the batch's seg_xpos / seg_xquat / sensordata arrays: the batch must outlive the controller (destroy the
+ * controller first), and nmf_cpg_advance_hybrid after the batch is gone reads freed memory. */
+int nmf_cpg_hybrid_enable(nmf_cpg* cpg, const nmf_cpg_hybrid_params* params, const float* corr, const uint8_t* swing, int root_seg,
+                          const int32_t tip_seg[6]);
+
+/* nmf_cpg_advance with the rules: reads the batch's seg_xpos / seg_xquat / sensordata itself, writes the launch's flags
+ * (NMF_CPG_RULE_FLAGS) and advances rho / sigma with the oscillators.  Argument checks and ONE kernel launch on `stream`: no
+ * allocation, no host synchronisation, hipGraph-capturable.  Refused: a controller without nmf_cpg_hybrid_enable, and everything
+ * nmf_cpg_advance refuses.  nmf_cpg_reset also zeroes rho / sigma / flags of the masked worlds once the rules are enabled. */
+int nmf_cpg_advance_hybrid(nmf_cpg* cpg, int n_steps, float* table_dev, int table_steps, void* stream);
 
 /* Odor intensity at n_sensors points rigidly attached to named segments (sensor_seg = index into the
  * batch's segment order, sensor_rel = offset in the segment frame): out[w][d][k] = sum_s peak[s][d] / dist^2.
