@@ -42,6 +42,7 @@ import numpy as np
 from . import _native
 from .anatomy import LEGS, JointDOF
 from .replay import MotionSnippet
+from .simulation import _field_view
 
 __all__ = ["TripodCPG", "TurningCPG", "HybridTurningCPG"]
 
@@ -210,6 +211,8 @@ class TurningCPG(TripodCPG):
     device state, writable between launches.  A new controller is reset: the tripod, world ``w`` at the phase offset ``w / n``.
     """
 
+    _advance_entry = "nmf_cpg_advance"                   # the library entry point behind :meth:`advance`
+
     def __init__(self, sim, fly_name: str, *, frequency: float = 12.0, coupling: float = 10.0, convergence: float = 20.0,
                  n_phase_bins: int = 256, adhesion=None, table_steps: int = 64):
         if hasattr(sim, "for_fly"):
@@ -249,17 +252,9 @@ class TurningCPG(TripodCPG):
                                      None if stance is None else stance.ctypes.data)
         if not self._h:
             raise _native.NativeError(lib.nmf_last_error().decode())
-        from .simulation import _tensor_from_ptr
-
+        self.phase, self.magnitude, self.drive = (_field_view(sim, lib.nmf_cpg_field_ptr, self._h, which, typestr)
+                                                  for which, typestr in ((0, "<f8"), (1, "<f4"), (2, "<f4")))
         t = sim._torch
-        views = []
-        for which, typestr in ((0, "<f8"), (1, "<f4"), (2, "<f4")):
-            width = ctypes.c_int32(0)
-            ptr = lib.nmf_cpg_field_ptr(self._h, which, ctypes.byref(width))
-            if not ptr:
-                raise _native.NativeError(lib.nmf_last_error().decode())
-            views.append(_tensor_from_ptr(t, ptr, (self.n_worlds, width.value), sim.device, typestr))
-        self.phase, self.magnitude, self.drive = views
         self.table = t.zeros((self.n_worlds, self.table_steps, self.n_act), dtype=t.float32, device=sim.device)
 
     # ---- lifecycle
@@ -321,7 +316,8 @@ class TurningCPG(TripodCPG):
         n = int(n_steps)
         if not 1 <= n <= self.table_steps:
             raise ValueError(f"n_steps must be in 1..{self.table_steps} (table_steps), got {n_steps}")
-        _native.check(_native.lib().nmf_cpg_advance(h, n, self.table.data_ptr(), self.table_steps, self.sim._stream()))
+        advance = getattr(_native.lib(), self._advance_entry)
+        _native.check(advance(h, n, self.table.data_ptr(), self.table_steps, self.sim._stream()))
         return self.table
 
     def step(self, n_steps: int, record_every: int | None = None):
@@ -374,8 +370,12 @@ class HybridTurningCPG(TurningCPG):
             columns of dofs outside the clip get 0.
 
     ``retraction`` and ``stumbling`` ``(n, 6)`` float32 and ``rule_flags`` ``(n, 6)`` uint8 (bit 0 retract, bit 1 stumble: the last
-    launch's decision) are zero-copy views; :meth:`reset` clears them for the masked worlds.
+    launch's decision) are zero-copy views; :meth:`reset` clears them for the masked worlds.  :meth:`advance` is
+    :meth:`TurningCPG.advance` with the rules: the launch decides from the batch's current pose and sensor outputs, writes
+    :attr:`rule_flags` and advances :attr:`retraction` / :attr:`stumbling` with the oscillators.
     """
+
+    _advance_entry = "nmf_cpg_advance_hybrid"
 
     def __init__(self, sim, fly_name: str, *, retraction_threshold: float = 0.05, stumbling_force_threshold: float = STUMBLING_DEFAULT,
                  retraction_rates=(800.0, 700.0), stumbling_rates=(2200.0, 1800.0), max_correction: float = 80.0,
@@ -427,27 +427,9 @@ class HybridTurningCPG(TurningCPG):
                                                *self.stumbling_rates, self.max_correction)
         _native.check(lib.nmf_cpg_hybrid_enable(self._h, ctypes.byref(self._hybrid_params), self.corr.ctypes.data,
                                                 self.swing.ctypes.data, self.root_seg, self.tip_seg.ctypes.data))
-        from .simulation import _tensor_from_ptr
-
-        views = []
-        for which, typestr in ((3, "<f4"), (4, "<f4"), (5, "|u1")):
-            width = ctypes.c_int32(0)
-            ptr = lib.nmf_cpg_field_ptr(self._h, which, ctypes.byref(width))
-            if not ptr:
-                raise _native.NativeError(lib.nmf_last_error().decode())
-            views.append(_tensor_from_ptr(sim._torch, ptr, (self.n_worlds, width.value), sim.device, typestr))
-        self.retraction, self.stumbling, self.rule_flags = views
+        self.retraction, self.stumbling, self.rule_flags = (_field_view(sim, lib.nmf_cpg_field_ptr, self._h, which, typestr)
+                                                            for which, typestr in ((3, "<f4"), (4, "<f4"), (5, "|u1")))
 
     def close(self) -> None:
         super().close()
         self.retraction = self.stumbling = self.rule_flags = None
-
-    def advance(self, n_steps: int):
-        """:meth:`TurningCPG.advance` with the rules: the launch decides from the batch's current pose and sensor outputs, writes
-        :attr:`rule_flags` and advances :attr:`retraction` / :attr:`stumbling` with the oscillators."""
-        h = self._handle()
-        n = int(n_steps)
-        if not 1 <= n <= self.table_steps:
-            raise ValueError(f"n_steps must be in 1..{self.table_steps} (table_steps), got {n_steps}")
-        _native.check(_native.lib().nmf_cpg_advance_hybrid(h, n, self.table.data_ptr(), self.table_steps, self.sim._stream()))
-        return self.table

@@ -3,8 +3,6 @@
 // Owns device memory for the model constants and the per-world state, launches the fused step
 // kernel (nmf_step.hip) and the gather/scatter kernels (nmf_batch_ops.hip).  No torch types, no host sync on the
 // stepping path.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -12,6 +10,10 @@
 #include <cstring>
 #include <string>
 #include <vector>
+
+// NMF_DEVMEM_CHECK: scripts/micro/devmem_check.cpp compiles this file up to DevMem alone, over host stand-ins for its HIP calls
+#ifndef NMF_DEVMEM_CHECK
+#include <hip/hip_runtime.h>
 
 #include "nmf.h"
 #include "nmf_batch_ops.hip"
@@ -21,6 +23,7 @@
 #include "nmf_camera.hip"
 #include "nmf_replay.hip"
 #include "nmf_cpg.hip"
+#endif
 
 namespace {
 
@@ -48,8 +51,45 @@ struct DeviceGuard {
   DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 #define DEVICE_GUARD(b)                                                                       \
-  DeviceGuard guard_((b)->device);                                                            \
+  DeviceGuard guard_((b)->mem.device);                                                        \
   if (guard_.err != hipSuccess) return fail(std::string("hipSetDevice: ") + hipGetErrorString(guard_.err))
+
+// The device memory of one handle (batch, eye plan, camera plan, CPG): every allocation is 16-byte granular, recorded, and freed
+// with the handle.  The first failure sets the error text, named after the entry point `who`, and sticks: later calls return
+// null without touching the device, so that a caller tests `ok` once after its last allocation.
+struct DevMem {
+  int device = 0;
+  const char* who = "";
+  bool ok = true;
+  std::vector<void*> ptrs;
+
+  void* alloc(size_t bytes) { return upload(nullptr, bytes); }       // zero-filled
+  void* upload(const void* src, size_t bytes) {                      // a copy of host memory (zeros where src is null)
+    if (!ok) return nullptr;
+    const size_t size = (std::max(bytes, (size_t)1) + 15) & ~(size_t)15;
+    void* p = nullptr;
+    if (hipMalloc(&p, size) != hipSuccess) { ok = false; fail(std::string(who) + ": out of device memory"); return nullptr; }
+    ptrs.push_back(p);
+    if ((src && bytes ? hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) : hipMemset(p, 0, size)) != hipSuccess) {
+      ok = false; fail(std::string(who) + ": the upload to the device failed"); return nullptr;
+    }
+    return p;
+  }
+  // Frees what was allocated since mark() and clears a failure since then: the handle is as it was at the mark
+  size_t mark() const { return ptrs.size(); }
+  void rollback(size_t mark) {
+    DeviceGuard guard(device);
+    for (size_t k = mark; k < ptrs.size(); ++k) (void)hipFree(ptrs[k]);      // (hipFree waits for the kernels that read them)
+    ptrs.resize(mark);
+    ok = true;
+  }
+  void release() { rollback(0); }
+};
+
+}  // namespace
+
+#ifndef NMF_DEVMEM_CHECK      // (to the end of the file)
+namespace {
 
 struct BlobEntry {
   char name[32];
@@ -64,6 +104,20 @@ struct HostArray {
   bool is_int = false;
   int64_t count = 0;
 };
+
+// The body of a *_create entry point: `fill` builds the fresh handle `h` with its device current.  If it fails the handle is
+// destroyed, the error text stays, and the caller gets null.
+template <class H, class Fill>
+H* build_or_destroy(int device, const char* who, H* h, void (*destroy)(H*), Fill&& fill) {
+  h->mem.device = device; h->mem.who = who;
+  DeviceGuard guard(device);
+  if (guard.err != hipSuccess) fail(std::string("hipSetDevice: ") + hipGetErrorString(guard.err));
+  else if (fill(h) == 0) return h;
+  const std::string keep = g_err;
+  destroy(h);
+  g_err = keep;
+  return nullptr;
+}
 
 }  // namespace
 
@@ -82,7 +136,7 @@ struct nmf_model {
 // ommatidia types — with its OWN device copies of the id map, the retina run plan, the pale flags and the normalisation, so that
 // a render call is pure stream-ordered work whatever the caller does with its buffers afterwards.
 struct nmf_eye_plan {
-  int device = 0, h = 0, w = 0, n_omm = 0;
+  int h = 0, w = 0, n_omm = 0;
   float fov = 0.f;
   int n_groups[3] = {0, 0, 0};                 // [0] chunks that feed an ommatidium, [1] all chunks (frames), [2] sampled mode: pixels
   int* visit[3] = {nullptr, nullptr, nullptr};
@@ -90,18 +144,18 @@ struct nmf_eye_plan {
   float* chunk_cones[3] = {nullptr, nullptr, nullptr};
   int* slot_omm = nullptr;
   int16_t* id_map = nullptr; void* rplan = nullptr; uint8_t* pale = nullptr; float* inv_norm = nullptr;      // the plan's copies
-  std::vector<void*> allocs;
+  DevMem mem;
   // cache key of nmf_eye_render's implicit plans: the caller's buffer addresses
   const void* key[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 struct nmf_batch {
   const nmf_model* model = nullptr;
-  int n_worlds = 0, device = 0, topo = 0;
+  int n_worlds = 0, topo = 0;
   nmf::DevModel dm{};
   nmf::DevModel* dm_dev = nullptr;
   nmf::DevState st{};
-  std::vector<void*> allocs;
+  DevMem mem;
   float* fields[NMF_FIELD_COUNT] = {};
   int widths[NMF_FIELD_COUNT] = {};
   int64_t steps = 0;
@@ -223,45 +277,34 @@ extern "C" int nmf_model_dims(const nmf_model* m, int32_t out[10]) {
 
 namespace {
 
+// The batch's copy of a host array.  `slot`: address of a DevModel pointer member (the device pass of this file sees those typed
+// as global memory, NMF_G).  A failure is the batch's to test (b->mem.ok).
 template <class T>
-int upload(nmf_batch* b, const std::vector<T>& host, const T** dev) {
-  void* p = nullptr;
-  size_t bytes = sizeof(T) * (host.empty() ? 1 : host.size());
-  HIP_OK(hipMalloc(&p, bytes));
-  b->allocs.push_back(p);
-  if (!host.empty()) HIP_OK(hipMemcpy(p, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice));
-  *dev = (const T*)p;
-  return 0;
+void upload(nmf_batch* b, const std::vector<T>& host, void* slot) {
+  const void* p = b->mem.upload(host.data(), sizeof(T) * host.size());
+  memcpy(slot, &p, sizeof(p));
 }
-
-// `slot`: address of a DevModel pointer member (the device pass of this file sees those typed as global memory, NMF_G)
 int upload_f(nmf_batch* b, const char* name, void* slot) {
   const HostArray* a = b->model->find(name);
   if (!a || a->is_int) return fail(std::string("model lacks float entry ") + name);
-  return upload(b, a->f, static_cast<const float**>(slot));
+  upload(b, a->f, slot);
+  return 0;
 }
 int upload_i(nmf_batch* b, const char* name, void* slot) {
   const HostArray* a = b->model->find(name);
   if (!a || !a->is_int) return fail(std::string("model lacks int entry ") + name);
-  return upload(b, a->i, static_cast<const int**>(slot));
-}
-
-// A device buffer of `count` T that lives as long as the batch, zeroed unless `zero` is false
-template <class T>
-int alloc_dev(nmf_batch* b, size_t count, T** out, bool zero = true) {
-  void* p = nullptr;
-  if (hipMalloc(&p, sizeof(T) * count) != hipSuccess) return fail("nmf_batch_create: out of device memory");
-  b->allocs.push_back(p);
-  *out = (T*)p;
-  if (zero) HIP_OK(hipMemset(p, 0, sizeof(T) * count));
+  upload(b, a->i, slot);
   return 0;
 }
 
-int alloc_field(nmf_batch* b, int field, int width, float** out) {
-  if (alloc_dev(b, (size_t)b->n_worlds * (size_t)(width > 0 ? width : 1), out) != 0) return -1;
+// A zeroed device buffer of `count` T that lives as long as the batch
+template <class T>
+void alloc_dev(nmf_batch* b, size_t count, T** out) { *out = (T*)b->mem.alloc(sizeof(T) * count); }
+
+void alloc_field(nmf_batch* b, int field, int width, float** out) {
+  alloc_dev(b, (size_t)b->n_worlds * (size_t)(width > 0 ? width : 1), out);
   b->fields[field] = *out;
   b->widths[field] = width;
-  return 0;
 }
 
 template <class T> struct TopoTag { using type = T; };
@@ -537,7 +580,7 @@ int fill_model(nmf_batch* b, const Skeleton& sk, const Options& opt) {
       // racing with the affine actuator that may share their dof; the general pass reads the dof from the row's flags
       std::vector<int> trn = model->find("act_trn")->i;
       for (int u = 0; u < model->nu; ++u) if ((int)ag->f[(size_t)u * nmf::kActGen] & 1) trn[(size_t)u] = 0;
-      rc |= upload(b, trn, reinterpret_cast<const int**>((void*)&d.act_trn));
+      upload(b, trn, &d.act_trn);
     }
   }
   UI(geom_body); UI(geom_type); UI(geom_hulladr); UI(geom_hullnum); UI(geom_sensor);
@@ -547,10 +590,10 @@ int fill_model(nmf_batch* b, const Skeleton& sk, const Options& opt) {
 #undef UI
   if (topo >= 2) {
     const HostArray* bp = model->find("body_parent");
-    rc |= upload(b, bp->i, reinterpret_cast<const int**>((void*)&d.body_parent));
-    rc |= upload(b, tree_body, reinterpret_cast<const int**>((void*)&d.tree_body));
-    rc |= upload(b, child_start, reinterpret_cast<const int**>((void*)&d.tree_child_start));
-    rc |= upload(b, child_count, reinterpret_cast<const int**>((void*)&d.tree_child_count));
+    upload(b, bp->i, &d.body_parent);
+    upload(b, tree_body, &d.tree_body);
+    upload(b, child_start, &d.tree_child_start);
+    upload(b, child_count, &d.tree_child_count);
     d.tree_nlevel = (int)lvl_start.size() - 1;
     for (size_t k = 0; k < 18; ++k) d.tree_lvl_start[k] = k < lvl_start.size() ? lvl_start[k] : (int)tree_body.size();
     d.rest_fast = 0; d.rest_pack = nullptr;
@@ -570,7 +613,7 @@ int fill_model(nmf_batch* b, const Skeleton& sk, const Options& opt) {
           pack[(size_t)((lv - 1) * 8 + (k - k0)) * 2 + 1] = child_start[(size_t)bb] | (k << 8);
         }
       }
-      if (fast) { d.rest_fast = 1; const int* pp = nullptr; rc |= upload(b, pack, &pp); *reinterpret_cast<const int**>((void*)&d.rest_pack) = pp; }
+      if (fast) { d.rest_fast = 1; upload(b, pack, &d.rest_pack); }
     }
   } else {
     d.body_parent = d.tree_body = d.tree_child_start = d.tree_child_count = nullptr; d.tree_nlevel = 0; d.rest_fast = 0; d.rest_pack = nullptr;
@@ -580,11 +623,8 @@ int fill_model(nmf_batch* b, const Skeleton& sk, const Options& opt) {
   d.max_contacts = nmf::kMaxCon;
   d.solver_flags = opt.solver & 7;
   if (rc != 0) return rc;
-  void* p = nullptr;
-  if (hipMalloc(&p, sizeof(nmf::DevModel)) != hipSuccess) return fail("nmf_batch_create: model upload failed");
-  b->allocs.push_back(p); b->dm_dev = (nmf::DevModel*)p;
-  if (hipMemcpy(p, &d, sizeof(nmf::DevModel), hipMemcpyHostToDevice) != hipSuccess) return fail("nmf_batch_create: model upload failed");
-  return 0;
+  b->dm_dev = (nmf::DevModel*)b->mem.upload(&d, sizeof(nmf::DevModel));
+  return b->mem.ok ? 0 : -1;
 }
 
 // DevState: the per-world fields and the stepping kernel's scratch
@@ -595,30 +635,29 @@ int alloc_state(nmf_batch* b) {
   st.n_worlds = b->n_worlds;
   float* stats_sum = nullptr;
   b->handoff_stride = (model->nq + 2 * model->nv + model->nu + 6 + nmf::kActHistWords + 63) / 64 * 64;      // state, controls, clock + 5 running sums, active-set history
-  if (alloc_field(b, NMF_QPOS, model->nq, &st.qpos) || alloc_field(b, NMF_QVEL, model->nv, &st.qvel) ||
-      alloc_field(b, NMF_CTRL, model->nu, &st.ctrl) || alloc_field(b, NMF_QACC_WARMSTART, model->nv, &st.qacc_ws) ||
-      alloc_field(b, NMF_SEG_XPOS, model->nseg * 3, &st.seg_xpos) || alloc_field(b, NMF_SEG_XQUAT, model->nseg * 4, &st.seg_xquat) ||
-      alloc_field(b, NMF_SITE_XPOS, model->nsite * 3, &st.site_xpos) || alloc_field(b, NMF_ACTUATOR_FORCE, model->nu, &st.actuator_force) ||
-      alloc_field(b, NMF_SENSORDATA, 96, &st.sensordata) || alloc_field(b, NMF_TIME, 1, &st.time) ||
-      alloc_field(b, NMF_STATS, 8, &st.stats) || alloc_field(b, NMF_QACC, model->nv, &st.qacc) || alloc_field(b, NMF_COST, 1, &st.cost) ||
-      alloc_field(b, NMF_STATS_SUM, 16, &stats_sum) ||        // uint32 counters
-      alloc_field(b, NMF_CONTACT_GEOM, nmf::kMaxCon, &st.contact_geom) || alloc_field(b, NMF_ACT, model->nu, &st.act) ||
-      alloc_dev(b, n_worlds, &b->order_buf, false) || alloc_dev(b, 1, &b->csched_buf) ||
-      alloc_dev(b, n_worlds * (size_t)b->handoff_stride, &b->handoff_buf) ||      // tag 0 = no launch's
-      alloc_dev(b, n_worlds * nmf::kActHistWords, &st.act_hist))
-    return -1;
+  alloc_field(b, NMF_QPOS, model->nq, &st.qpos); alloc_field(b, NMF_QVEL, model->nv, &st.qvel);
+  alloc_field(b, NMF_CTRL, model->nu, &st.ctrl); alloc_field(b, NMF_QACC_WARMSTART, model->nv, &st.qacc_ws);
+  alloc_field(b, NMF_SEG_XPOS, model->nseg * 3, &st.seg_xpos); alloc_field(b, NMF_SEG_XQUAT, model->nseg * 4, &st.seg_xquat);
+  alloc_field(b, NMF_SITE_XPOS, model->nsite * 3, &st.site_xpos); alloc_field(b, NMF_ACTUATOR_FORCE, model->nu, &st.actuator_force);
+  alloc_field(b, NMF_SENSORDATA, 96, &st.sensordata); alloc_field(b, NMF_TIME, 1, &st.time);
+  alloc_field(b, NMF_STATS, 8, &st.stats); alloc_field(b, NMF_QACC, model->nv, &st.qacc); alloc_field(b, NMF_COST, 1, &st.cost);
+  alloc_field(b, NMF_STATS_SUM, 16, &stats_sum);        // uint32 counters
+  alloc_field(b, NMF_CONTACT_GEOM, nmf::kMaxCon, &st.contact_geom); alloc_field(b, NMF_ACT, model->nu, &st.act);
+  alloc_dev(b, n_worlds, &b->order_buf); alloc_dev(b, 1, &b->csched_buf);
+  alloc_dev(b, n_worlds * (size_t)b->handoff_stride, &b->handoff_buf);      // tag 0 = no launch's
+  alloc_dev(b, n_worlds * nmf::kActHistWords, &st.act_hist);
   st.stats_sum = reinterpret_cast<unsigned int*>(stats_sum);
   st.dual_scratch = nullptr;
   // ALL_POSSIBLE: the contact-space solve's leg factors live in HBM, one block per workgroup of a launch (<= n_worlds)
-  if (b->topo == 5 && alloc_dev(b, n_worlds * nmf::kDualScratchFloats, &st.dual_scratch, false)) return -1;
+  if (b->topo == 5) alloc_dev(b, n_worlds * nmf::kDualScratchFloats, &st.dual_scratch);
   st.noslip_buf = nullptr;
   // CPU flavour: scratch of the primal path's noslip pass (157 KB per world)
-  if (b->dm.noslip_iter > 0 && alloc_dev(b, n_worlds * nmf::kNoslipFloats, &st.noslip_buf)) return -1;
-  if (alloc_dev(b, 2, &b->clock_probe_buf) || alloc_dev(b, 1, &b->sched_buf)) return -1;
+  if (b->dm.noslip_iter > 0) alloc_dev(b, n_worlds * nmf::kNoslipFloats, &st.noslip_buf);
+  alloc_dev(b, 2, &b->clock_probe_buf); alloc_dev(b, 1, &b->sched_buf);
   st.clock_probe = b->clock_probe_buf;
   st.sched = nullptr;
   st.order = nullptr;
-  return 0;
+  return b->mem.ok ? 0 : -1;
 }
 
 // The chunk plan and the world order of launch()
@@ -645,7 +684,7 @@ void set_schedule(nmf_batch* b, const Options& opt) {
 // kernel this batch will launch (LDS- or register-limited, whichever binds); fallback = the LDS-limited figures of the
 // shipped build
 int pick_kernel(nmf_batch* b, const Options& opt) {
-  const int topo = b->topo, device = b->device;
+  const int topo = b->topo, device = b->mem.device;
   int per_cu = topo < 2 ? 8 : (topo == 2 ? 4 : (topo == 3 ? 3 : (topo == 4 ? 8 : 5)));
   const bool weld = b->dm.weld_active != 0, terrain = b->dm.terrain_type != 0;
   if (weld && terrain) return fail("nmf_batch_create: a tethered world has no terrain");
@@ -698,7 +737,8 @@ extern "C" nmf_batch* nmf_batch_create_ex(const nmf_model* model, int n_worlds, 
   if (guard.err != hipSuccess) { fail("nmf_batch_create: hipSetDevice failed (no MI355X visible?)"); return nullptr; }
   const Options opt = read_options(in);
   auto* b = new nmf_batch();
-  b->model = model; b->n_worlds = n_worlds; b->device = device; b->topo = sk.topo;
+  b->model = model; b->n_worlds = n_worlds; b->topo = sk.topo;
+  b->mem.device = device; b->mem.who = "nmf_batch_create";
   if (fill_model(b, sk, opt) != 0 || alloc_state(b) != 0 || (set_schedule(b, opt), pick_kernel(b, opt)) != 0 ||
       nmf_reset(b, nullptr) != 0 || hipDeviceSynchronize() != hipSuccess) {
     const std::string keep = g_err.empty() ? std::string("nmf_batch_create: device initialisation failed") : g_err;
@@ -711,8 +751,7 @@ extern "C" nmf_batch* nmf_batch_create_ex(const nmf_model* model, int n_worlds, 
 
 extern "C" void nmf_batch_destroy(nmf_batch* b) {
   if (!b) return;
-  DeviceGuard guard(b->device);
-  for (void* p : b->allocs) (void)hipFree(p);
+  b->mem.release();
   for (nmf_eye_plan* q : b->eye_plans) nmf_eye_plan_destroy(q);
   delete b;
 }
@@ -916,8 +955,7 @@ extern "C" size_t nmf_eye_params_size(void) { return sizeof(nmf_eye_params); }
 // sin of the half-angle) — so that a wave can decide per group what it can see at all.  Built on the host once per id map.
 extern "C" void nmf_eye_plan_destroy(nmf_eye_plan* P) {
   if (!P) return;
-  DeviceGuard guard(P->device);
-  for (void* q : P->allocs) (void)hipFree(q);      // (hipFree waits for the kernels that read them)
+  P->mem.release();
   delete P;
 }
 
@@ -925,7 +963,6 @@ extern "C" void nmf_eye_plan_destroy(nmf_eye_plan* P) {
 // per (id map, lens, ommatidia types).  Every failure path gives back what was allocated (nmf_eye_plan_destroy).
 static int fill_eye_plan(nmf_eye_plan* Pp, const int16_t* id_map_dev, const void* plan_dev, const uint8_t* pale_dev, const float* inv_norm_dev, int h, int w, float fov_deg, int n_omm) {
   nmf_eye_plan& P = *Pp;
-  auto dev_alloc = [&](size_t bytes) -> void* { void* q = nullptr; if (hipMalloc(&q, bytes) != hipSuccess) return nullptr; P.allocs.push_back(q); return q; };
   const int n_pix = h * w, n_chunk = n_pix / 16;
   std::vector<int16_t> ids((size_t)n_pix);
   HIP_OK(hipMemcpy(ids.data(), id_map_dev, sizeof(int16_t) * (size_t)n_pix, hipMemcpyDeviceToHost));
@@ -984,12 +1021,10 @@ static int fill_eye_plan(nmf_eye_plan* Pp, const int16_t* id_map_dev, const void
       cones[(size_t)g * 12 + 8] = g >= g_plain ? 1.f : 0.f;
       cones[(size_t)g * 12 + 9] = lens_ok ? 1.f : 0.f;      // [9]: every ray of the IMAGE within the range of the kernel's lens polynomials
     }
-    void* pv = dev_alloc(sizeof(int) * visit.size()); void* pc = dev_alloc(sizeof(float) * cones.size()); void* pcc = dev_alloc(sizeof(float) * ccones.size());
-    if (!pv || !pc || !pcc) return fail("nmf_eye_plan_create: out of device memory for the visit plan");
-    HIP_OK(hipMemcpy(pv, visit.data(), sizeof(int) * visit.size(), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(pc, cones.data(), sizeof(float) * cones.size(), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(pcc, ccones.data(), sizeof(float) * ccones.size(), hipMemcpyHostToDevice));
-    P.visit[mode] = (int*)pv; P.cones[mode] = (float*)pc; P.chunk_cones[mode] = (float*)pcc; P.n_groups[mode] = n_groups;
+    P.visit[mode] = (int*)P.mem.upload(visit.data(), sizeof(int) * visit.size());
+    P.cones[mode] = (float*)P.mem.upload(cones.data(), sizeof(float) * cones.size());
+    P.chunk_cones[mode] = (float*)P.mem.upload(ccones.data(), sizeof(float) * ccones.size());
+    P.n_groups[mode] = n_groups;
   }
   {
     // Sampled mode (nmf_eye_params::rays_per_ommatidium = 16): per ommatidium i the pixels of its cell in raster order,
@@ -1047,21 +1082,18 @@ static int fill_eye_plan(nmf_eye_plan* Pp, const int16_t* id_map_dev, const void
         cone_of(tp, 1e-4, &tcones[((size_t)g * (S / 4) + t) * 4]);
       }
     }
-    void* pv = dev_alloc(sizeof(int) * visit.size()); void* pc = dev_alloc(sizeof(float) * cones.size());
-    void* ps = dev_alloc(sizeof(int) * slots.size()); void* pt = dev_alloc(sizeof(float) * tcones.size());
-    if (!pv || !pc || !ps || !pt) return fail("nmf_eye_plan_create: out of device memory for the sampling plan");
-    HIP_OK(hipMemcpy(pt, tcones.data(), sizeof(float) * tcones.size(), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(pv, visit.data(), sizeof(int) * visit.size(), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(pc, cones.data(), sizeof(float) * cones.size(), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(ps, slots.data(), sizeof(int) * slots.size(), hipMemcpyHostToDevice));
-    P.visit[2] = (int*)pv; P.cones[2] = (float*)pc; P.chunk_cones[2] = (float*)pt; P.n_groups[2] = n_groups; P.slot_omm = (int*)ps;
+    P.visit[2] = (int*)P.mem.upload(visit.data(), sizeof(int) * visit.size());
+    P.cones[2] = (float*)P.mem.upload(cones.data(), sizeof(float) * cones.size());
+    P.chunk_cones[2] = (float*)P.mem.upload(tcones.data(), sizeof(float) * tcones.size());
+    P.slot_omm = (int*)P.mem.upload(slots.data(), sizeof(int) * slots.size());
+    P.n_groups[2] = n_groups;
   }
   // the plan's own copies of what the kernel reads from the caller's buffers
   {
     const size_t rbytes = nmf_retina_plan_bytes(n_pix);
-    P.id_map = (int16_t*)dev_alloc(sizeof(int16_t) * (size_t)n_pix); P.rplan = dev_alloc(rbytes);
-    P.pale = (uint8_t*)dev_alloc(((size_t)n_omm + 15) & ~(size_t)15); P.inv_norm = (float*)dev_alloc(sizeof(float) * (size_t)n_omm);
-    if (!P.id_map || !P.rplan || !P.pale || !P.inv_norm) return fail("nmf_eye_plan_create: out of device memory for the plan's copies");
+    P.id_map = (int16_t*)P.mem.alloc(sizeof(int16_t) * (size_t)n_pix); P.rplan = P.mem.alloc(rbytes);
+    P.pale = (uint8_t*)P.mem.alloc((size_t)n_omm); P.inv_norm = (float*)P.mem.alloc(sizeof(float) * (size_t)n_omm);
+    if (!P.mem.ok) return -1;
     HIP_OK(hipMemcpy(P.id_map, id_map_dev, sizeof(int16_t) * (size_t)n_pix, hipMemcpyDeviceToDevice));
     HIP_OK(hipMemcpy(P.rplan, plan_dev, rbytes, hipMemcpyDeviceToDevice));
     HIP_OK(hipMemcpy(P.pale, pale_dev, (size_t)n_omm, hipMemcpyDeviceToDevice));
@@ -1081,16 +1113,9 @@ extern "C" nmf_eye_plan* nmf_eye_plan_create(const int16_t* id_map_dev, const vo
   if (reinterpret_cast<uintptr_t>(plan_dev) & 15u) { fail("nmf_eye_plan_create: the run plan must be 16-byte aligned"); return nullptr; }
   int n_dev = 0;
   if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) { fail("nmf_eye_plan_create: no such device"); return nullptr; }
-  DeviceGuard guard(device);
-  nmf_eye_plan* P = new nmf_eye_plan();
-  P->device = device;
-  if (fill_eye_plan(P, id_map_dev, plan_dev, pale_dev, inv_norm_dev, height, width, fov_deg, n_ommatidia) != 0) {
-    const std::string keep = g_err;
-    nmf_eye_plan_destroy(P);
-    g_err = keep;
-    return nullptr;
-  }
-  return P;
+  return build_or_destroy(device, "nmf_eye_plan_create", new nmf_eye_plan(), nmf_eye_plan_destroy, [&](nmf_eye_plan* P) {
+    return fill_eye_plan(P, id_map_dev, plan_dev, pale_dev, inv_norm_dev, height, width, fov_deg, n_ommatidia);
+  });
 }
 
 // Pure stream-ordered work: argument checks on the host, one kernel launch.  Everything the kernel reads besides the batch's poses and
@@ -1099,7 +1124,7 @@ extern "C" int nmf_eye_render_planned(nmf_batch* b, const nmf_eye_params* p, con
                                       const int32_t* capsule_seg_dev, const float* capsule_geom_dev,
                                       uint8_t* frames_out_dev, float* omm_out_dev, void* stream) {
   if (!b || !p || !plan) return fail("nmf_eye_render: null batch / params / plan");
-  if (plan->device != b->device) return fail("nmf_eye_render: the plan lives on another device than the batch");
+  if (plan->mem.device != b->mem.device) return fail("nmf_eye_render: the plan lives on another device than the batch");
   if (plan->h != p->height || plan->w != p->width || plan->fov != p->fov_deg) return fail("nmf_eye_render: the plan was made for another frame size / field of view");
   const int n_ommatidia = plan->n_omm;
   const int16_t* const id_map_dev = plan->id_map; const void* const plan_dev = plan->rplan; const uint8_t* const pale_dev = plan->pale; const float* const inv_norm_dev = plan->inv_norm;
@@ -1162,19 +1187,18 @@ extern "C" int nmf_eye_render_planned(nmf_batch* b, const nmf_eye_params* p, con
 // Everything a render needs besides the batch's poses and the caller's spheres: an explicit handle with its own device copies.
 struct nmf_camera_plan {
   const nmf_batch* batch = nullptr;
-  int device = 0, n_cameras = 0, n_selected = 0, n_caps = 0;
+  int n_cameras = 0, n_selected = 0, n_caps = 0;
   nmf::CamArgs args{};
   bool spheres_per_world = false;
   nmf::CamView* views = nullptr; int* world_ids = nullptr; int* cap_seg = nullptr; float* cap_geom = nullptr; unsigned int* cap_rgb = nullptr;
-  std::vector<void*> allocs;
+  DevMem mem;
 };
 
 extern "C" size_t nmf_camera_params_size(void) { return sizeof(nmf_camera_params); }
 
 extern "C" void nmf_camera_plan_destroy(nmf_camera_plan* P) {
   if (!P) return;
-  DeviceGuard guard(P->device);
-  for (void* q : P->allocs) (void)hipFree(q);      // (hipFree waits for the kernels that read them)
+  P->mem.release();
   delete P;
 }
 
@@ -1232,19 +1256,12 @@ static int fill_camera_plan(nmf_camera_plan* P, const nmf_batch* b, const nmf_ca
   P->n_cameras = n_cameras; P->n_selected = n_selected; P->n_caps = n_caps;
   std::vector<unsigned int> rgbw((size_t)std::max(n_caps, 1), 0u);
   for (int c = 0; c < n_caps; ++c) rgbw[(size_t)c] = (unsigned int)cap_rgb[3 * c] | ((unsigned int)cap_rgb[3 * c + 1] << 8) | ((unsigned int)cap_rgb[3 * c + 2] << 16);
-  auto upload = [&](const void* src, size_t bytes) -> void* {
-    void* q = nullptr;
-    if (hipMalloc(&q, std::max(bytes, (size_t)16)) != hipSuccess) return nullptr;
-    P->allocs.push_back(q);
-    if (bytes && hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return q;
-  };
-  P->views = (nmf::CamView*)upload(views.data(), sizeof(nmf::CamView) * views.size());
-  P->world_ids = (int*)upload(world_ids, sizeof(int) * (size_t)n_selected);
-  P->cap_seg = (int*)upload(cap_seg, sizeof(int) * (size_t)n_caps);
-  P->cap_geom = (float*)upload(cap_geom, sizeof(float) * 7 * (size_t)n_caps);
-  P->cap_rgb = (unsigned int*)upload(rgbw.data(), sizeof(unsigned int) * (size_t)n_caps);
-  if (!P->views || !P->world_ids || !P->cap_seg || !P->cap_geom || !P->cap_rgb) return fail("nmf_camera_plan_create: out of device memory for the plan's copies");
+  P->views = (nmf::CamView*)P->mem.upload(views.data(), sizeof(nmf::CamView) * views.size());
+  P->world_ids = (int*)P->mem.upload(world_ids, sizeof(int) * (size_t)n_selected);
+  P->cap_seg = (int*)P->mem.upload(cap_seg, sizeof(int) * (size_t)n_caps);
+  P->cap_geom = (float*)P->mem.upload(cap_geom, sizeof(float) * 7 * (size_t)n_caps);
+  P->cap_rgb = (unsigned int*)P->mem.upload(rgbw.data(), sizeof(unsigned int) * (size_t)n_caps);
+  if (!P->mem.ok) return -1;
   HIP_OK(hipDeviceSynchronize());
   return 0;
 }
@@ -1252,17 +1269,10 @@ static int fill_camera_plan(nmf_camera_plan* P, const nmf_batch* b, const nmf_ca
 extern "C" nmf_camera_plan* nmf_camera_plan_create(nmf_batch* b, const nmf_camera_params* p, int n_cameras, const int32_t* world_ids, int n_selected,
                                                    const int32_t* cap_seg, const float* cap_geom, const uint8_t* cap_rgb, int n_caps) {
   if (!b || !p) { fail("nmf_camera_plan_create: null batch / params"); return nullptr; }
-  DeviceGuard guard(b->device);
-  if (guard.err != hipSuccess) { fail(std::string("hipSetDevice: ") + hipGetErrorString(guard.err)); return nullptr; }
-  nmf_camera_plan* P = new nmf_camera_plan();
-  P->batch = b; P->device = b->device;
-  if (fill_camera_plan(P, b, p, n_cameras, world_ids, n_selected, cap_seg, cap_geom, cap_rgb, n_caps) != 0) {
-    const std::string keep = g_err;
-    nmf_camera_plan_destroy(P);
-    g_err = keep;
-    return nullptr;
-  }
-  return P;
+  return build_or_destroy(b->mem.device, "nmf_camera_plan_create", new nmf_camera_plan(), nmf_camera_plan_destroy, [&](nmf_camera_plan* P) {
+    P->batch = b;
+    return fill_camera_plan(P, b, p, n_cameras, world_ids, n_selected, cap_seg, cap_geom, cap_rgb, n_caps);
+  });
 }
 
 // Pure stream-ordered work: argument checks on the host, one kernel launch.
@@ -1300,7 +1310,7 @@ extern "C" int nmf_eye_render(nmf_batch* b, const nmf_eye_params* p, const float
         q->fov == p->fov_deg && q->n_omm == n_ommatidia) { plan = q; L.erase(L.begin() + (long)i); L.push_back(q); break; }
   }
   if (!plan) {
-    plan = nmf_eye_plan_create(id_map_dev, plan_dev, pale_dev, inv_norm_dev, p->height, p->width, p->fov_deg, n_ommatidia, b->device);
+    plan = nmf_eye_plan_create(id_map_dev, plan_dev, pale_dev, inv_norm_dev, p->height, p->width, p->fov_deg, n_ommatidia, b->mem.device);
     if (!plan) return -1;
     plan->key[0] = id_map_dev; plan->key[1] = plan_dev; plan->key[2] = pale_dev; plan->key[3] = inv_norm_dev;
     if (L.size() >= 4) { nmf_eye_plan_destroy(L.front()); L.erase(L.begin()); }
@@ -1312,7 +1322,7 @@ extern "C" int nmf_eye_render(nmf_batch* b, const nmf_eye_params* p, const float
 // ---- closed-loop tripod CPG (nmf_cpg.hip) ----
 // The controller's shared tables (own device copies) and its per-world state.
 struct nmf_cpg {
-  int device = 0, n_worlds = 0, table_steps = 0;
+  int n_worlds = 0, table_steps = 0;
   nmf::CpgArgs args{};
   float* cycle = nullptr; float* mean = nullptr; int* leg_of_col = nullptr; uint8_t* stance = nullptr;
   double* phase = nullptr; float* mag = nullptr; double* mag_acc = nullptr; float* drive = nullptr;   // mag_acc: the magnitudes' float64 sums
@@ -1321,15 +1331,14 @@ struct nmf_cpg {
   bool hybrid = false;
   nmf::CpgHybridArgs hargs{};
   nmf::CpgHybridPtrs hptrs{};
-  std::vector<void*> allocs;
+  DevMem mem;
 };
 
 extern "C" size_t nmf_cpg_params_size(void) { return sizeof(nmf_cpg_params); }
 
 extern "C" void nmf_cpg_destroy(nmf_cpg* C) {
   if (!C) return;
-  DeviceGuard guard(C->device);
-  for (void* q : C->allocs) (void)hipFree(q);      // (hipFree waits for the kernels that read them)
+  C->mem.release();
   delete C;
 }
 
@@ -1338,11 +1347,12 @@ extern "C" int nmf_cpg_reset(nmf_cpg* C, const uint8_t* mask_dev, int first_worl
   if (first_world < 0 || total_worlds < 1 || (int64_t)first_world + C->n_worlds > (int64_t)total_worlds)
     return fail("nmf_cpg_reset: the controller's worlds [first_world, first_world + n_worlds) must lie inside [0, total_worlds)");
   DEVICE_GUARD(C);
-  hipLaunchKernelGGL(nmf::nmf_cpg_reset_kernel, dim3((unsigned)((6 * C->n_worlds + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  const dim3 grid((unsigned)((6 * C->n_worlds + 255) / 256)), block(256);
+  hipLaunchKernelGGL(nmf::nmf_cpg_reset_kernel, grid, block, 0, (hipStream_t)stream,
                      C->n_worlds, mask_dev, first_world, total_worlds, C->phase, C->mag, C->mag_acc, C->drive);
   HIP_OK(hipGetLastError());
   if (C->hybrid) {
-    hipLaunchKernelGGL(nmf::nmf_cpg_hybrid_reset_kernel, dim3((unsigned)((6 * C->n_worlds + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(nmf::nmf_cpg_hybrid_reset_kernel, grid, block, 0, (hipStream_t)stream,
                        C->n_worlds, mask_dev, C->hptrs.retraction, C->hptrs.stumbling, C->hptrs.flags);
     HIP_OK(hipGetLastError());
   }
@@ -1369,24 +1379,16 @@ static int fill_cpg(nmf_cpg* C, const nmf_cpg_params* p, const float* cycle, con
     for (int i = 0; i < p->n_bins; ++i) sum += (double)cycle[(size_t)i * p->n_pos + c];
     mean[(size_t)c] = (float)(sum / (double)p->n_bins);
   }
-  auto alloc = [&](const void* src, size_t bytes) -> void* {
-    void* q = nullptr;
-    if (hipMalloc(&q, std::max(bytes, (size_t)16)) != hipSuccess) return nullptr;
-    C->allocs.push_back(q);
-    if (src && hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return q;
-  };
   const size_t n = (size_t)C->n_worlds;
-  C->cycle = (float*)alloc(cycle, sizeof(float) * (size_t)p->n_bins * (size_t)p->n_pos);
-  C->mean = (float*)alloc(mean.data(), sizeof(float) * mean.size());
-  C->leg_of_col = (int*)alloc(leg_of_col, sizeof(int) * (size_t)p->n_pos);
-  C->stance = (uint8_t*)alloc(stance, stance ? (size_t)p->n_bins * 6 : 0);
-  C->phase = (double*)alloc(nullptr, sizeof(double) * 6 * n);
-  C->mag = (float*)alloc(nullptr, sizeof(float) * 6 * n);
-  C->mag_acc = (double*)alloc(nullptr, sizeof(double) * 6 * n);
-  C->drive = (float*)alloc(nullptr, sizeof(float) * 2 * n);
-  if (!C->cycle || !C->mean || !C->leg_of_col || !C->stance || !C->phase || !C->mag || !C->mag_acc || !C->drive)
-    return fail("nmf_cpg_create: out of device memory");
+  C->cycle = (float*)C->mem.upload(cycle, sizeof(float) * (size_t)p->n_bins * (size_t)p->n_pos);
+  C->mean = (float*)C->mem.upload(mean.data(), sizeof(float) * mean.size());
+  C->leg_of_col = (int*)C->mem.upload(leg_of_col, sizeof(int) * (size_t)p->n_pos);
+  C->stance = (uint8_t*)C->mem.upload(stance, stance ? (size_t)p->n_bins * 6 : 0);
+  C->phase = (double*)C->mem.alloc(sizeof(double) * 6 * n);
+  C->mag = (float*)C->mem.alloc(sizeof(float) * 6 * n);
+  C->mag_acc = (double*)C->mem.alloc(sizeof(double) * 6 * n);
+  C->drive = (float*)C->mem.alloc(sizeof(float) * 2 * n);
+  if (!C->mem.ok) return -1;
   if (nmf_cpg_reset(C, nullptr, 0, C->n_worlds, nullptr) != 0) return -1;
   HIP_OK(hipDeviceSynchronize());
   return 0;
@@ -1394,17 +1396,10 @@ static int fill_cpg(nmf_cpg* C, const nmf_cpg_params* p, const float* cycle, con
 
 extern "C" nmf_cpg* nmf_cpg_create(nmf_batch* b, const nmf_cpg_params* p, const float* cycle, const int32_t* leg_of_col, const uint8_t* stance) {
   if (!b || !p) { fail("nmf_cpg_create: null batch / params"); return nullptr; }
-  DeviceGuard guard(b->device);
-  if (guard.err != hipSuccess) { fail(std::string("hipSetDevice: ") + hipGetErrorString(guard.err)); return nullptr; }
-  nmf_cpg* C = new nmf_cpg();
-  C->device = b->device; C->n_worlds = b->n_worlds; C->batch = b;
-  if (fill_cpg(C, p, cycle, leg_of_col, stance) != 0) {
-    const std::string keep = g_err;
-    nmf_cpg_destroy(C);
-    g_err = keep;
-    return nullptr;
-  }
-  return C;
+  return build_or_destroy(b->mem.device, "nmf_cpg_create", new nmf_cpg(), nmf_cpg_destroy, [&](nmf_cpg* C) {
+    C->n_worlds = b->n_worlds; C->batch = b;
+    return fill_cpg(C, p, cycle, leg_of_col, stance);
+  });
 }
 
 extern "C" void* nmf_cpg_field_ptr(nmf_cpg* C, int which, int32_t* width) {
@@ -1417,8 +1412,8 @@ extern "C" void* nmf_cpg_field_ptr(nmf_cpg* C, int which, int32_t* width) {
   return ptr[which];
 }
 
-// Pure stream-ordered work: argument checks on the host, one kernel launch.
-static int cpg_advance_checks(const char* who, nmf_cpg* C, int n_steps, float* table_dev, int table_steps, void* stream) {
+// Pure stream-ordered work: argument checks on the host, one kernel launch (with the hybrid rules or without).
+static int cpg_advance(const char* who, bool hybrid, nmf_cpg* C, int n_steps, float* table_dev, int table_steps, void* stream) {
   const std::string w(who);
   if (!C) return fail(w + ": null controller");
   if (!table_dev) return fail(w + ": null table");
@@ -1430,18 +1425,22 @@ static int cpg_advance_checks(const char* who, nmf_cpg* C, int n_steps, float* t
   if (hipStreamIsCapturing((hipStream_t)stream, &capturing) == hipSuccess && capturing == hipStreamCaptureStatusNone) {
     hipPointerAttribute_t at{};
     if (hipPointerGetAttributes(&at, table_dev) != hipSuccess) { (void)hipGetLastError(); return fail(w + ": the table is not device memory"); }
-    if (at.device != C->device) return fail(w + ": the controller was made for device " + std::to_string(C->device) + ", the table is on device " + std::to_string(at.device));
+    if (at.device != C->mem.device) return fail(w + ": the controller was made for device " + std::to_string(C->mem.device) + ", the table is on device " + std::to_string(at.device));
   }
+  if (hybrid && !C->hybrid) return fail(w + ": the hybrid rules are not enabled (nmf_cpg_hybrid_enable)");
+  const dim3 grid((unsigned)((C->n_worlds + nmf::kCpgWorlds - 1) / nmf::kCpgWorlds)), block(nmf::kCpgThreads);
+  if (hybrid)
+    hipLaunchKernelGGL(nmf::nmf_cpg_advance_hybrid_kernel, grid, block, 0, (hipStream_t)stream, C->args, C->hargs, C->hptrs, C->cycle, C->mean,
+                       C->leg_of_col, C->stance, C->drive, C->phase, C->mag, C->mag_acc, table_dev, table_steps, n_steps);
+  else
+    hipLaunchKernelGGL(nmf::nmf_cpg_advance_kernel, grid, block, 0, (hipStream_t)stream, C->args, C->cycle, C->mean, C->leg_of_col, C->stance,
+                       C->drive, C->phase, C->mag, C->mag_acc, table_dev, table_steps, n_steps);
+  HIP_OK(hipGetLastError());
   return 0;
 }
 
 extern "C" int nmf_cpg_advance(nmf_cpg* C, int n_steps, float* table_dev, int table_steps, void* stream) {
-  if (cpg_advance_checks("nmf_cpg_advance", C, n_steps, table_dev, table_steps, stream) != 0) return -1;
-  DEVICE_GUARD(C);
-  hipLaunchKernelGGL(nmf::nmf_cpg_advance_kernel, dim3((unsigned)((C->n_worlds + nmf::kCpgWorlds - 1) / nmf::kCpgWorlds)), dim3(nmf::kCpgThreads), 0,
-                     (hipStream_t)stream, C->args, C->cycle, C->mean, C->leg_of_col, C->stance, C->drive, C->phase, C->mag, C->mag_acc, table_dev, table_steps, n_steps);
-  HIP_OK(hipGetLastError());
-  return 0;
+  return cpg_advance("nmf_cpg_advance", false, C, n_steps, table_dev, table_steps, stream);
 }
 
 // ---- the hybrid rules of the CPG (retraction, stumbling) ----
@@ -1473,26 +1472,19 @@ extern "C" int nmf_cpg_hybrid_enable(nmf_cpg* C, const nmf_cpg_hybrid_params* p,
   H.up_r = (float)(C->args.timestep * (double)p->retraction_up); H.down_r = (float)(C->args.timestep * (double)p->retraction_down);
   H.up_s = (float)(C->args.timestep * (double)p->stumbling_up); H.down_s = (float)(C->args.timestep * (double)p->stumbling_down);
   H.cap = p->max_correction;
-  auto alloc = [&](const void* src, size_t bytes) -> void* {
-    void* q = nullptr;
-    if (hipMalloc(&q, std::max(bytes, (size_t)16)) != hipSuccess) return nullptr;
-    C->allocs.push_back(q);
-    if ((src ? hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) : hipMemset(q, 0, bytes)) != hipSuccess) return nullptr;
-    return q;
-  };
-  const size_t n = (size_t)C->n_worlds, n_allocs = C->allocs.size();
+  const size_t n = (size_t)C->n_worlds, mark = C->mem.mark();
+  C->mem.who = "nmf_cpg_hybrid_enable";
   nmf::CpgHybridPtrs P{};
-  P.corr = (const float*)alloc(corr, sizeof(float) * (size_t)C->args.n_pos);
-  P.swing = (const uint8_t*)alloc(swing, (size_t)C->args.n_bins * 6);
-  P.retraction = (float*)alloc(nullptr, sizeof(float) * 6 * n);
-  P.stumbling = (float*)alloc(nullptr, sizeof(float) * 6 * n);
-  P.flags = (uint8_t*)alloc(nullptr, 6 * n);
+  P.corr = (const float*)C->mem.upload(corr, sizeof(float) * (size_t)C->args.n_pos);
+  P.swing = (const uint8_t*)C->mem.upload(swing, (size_t)C->args.n_bins * 6);
+  P.retraction = (float*)C->mem.alloc(sizeof(float) * 6 * n);
+  P.stumbling = (float*)C->mem.alloc(sizeof(float) * 6 * n);
+  P.flags = (uint8_t*)C->mem.alloc(6 * n);
   P.seg_xpos = b->st.seg_xpos; P.seg_xquat = b->st.seg_xquat; P.sensordata = b->st.sensordata;
-  if (!P.corr || !P.swing || !P.retraction || !P.stumbling || !P.flags) {
+  if (!C->mem.ok) {
     (void)hipGetLastError();
-    for (size_t k = n_allocs; k < C->allocs.size(); ++k) (void)hipFree(C->allocs[k]);   // the controller stays as it was
-    C->allocs.resize(n_allocs);
-    return fail("nmf_cpg_hybrid_enable: out of device memory");
+    C->mem.rollback(mark);        // the controller stays as it was
+    return -1;
   }
   HIP_OK(hipDeviceSynchronize());
   C->hargs = H;
@@ -1502,14 +1494,7 @@ extern "C" int nmf_cpg_hybrid_enable(nmf_cpg* C, const nmf_cpg_hybrid_params* p,
 }
 
 extern "C" int nmf_cpg_advance_hybrid(nmf_cpg* C, int n_steps, float* table_dev, int table_steps, void* stream) {
-  if (cpg_advance_checks("nmf_cpg_advance_hybrid", C, n_steps, table_dev, table_steps, stream) != 0) return -1;
-  if (!C->hybrid) return fail("nmf_cpg_advance_hybrid: the hybrid rules are not enabled (nmf_cpg_hybrid_enable)");
-  DEVICE_GUARD(C);
-  hipLaunchKernelGGL(nmf::nmf_cpg_advance_hybrid_kernel, dim3((unsigned)((C->n_worlds + nmf::kCpgWorlds - 1) / nmf::kCpgWorlds)), dim3(nmf::kCpgThreads), 0,
-                     (hipStream_t)stream, C->args, C->hargs, C->hptrs, C->cycle, C->mean, C->leg_of_col, C->stance, C->drive, C->phase, C->mag, C->mag_acc,
-                     table_dev, table_steps, n_steps);
-  HIP_OK(hipGetLastError());
-  return 0;
+  return cpg_advance("nmf_cpg_advance_hybrid", true, C, n_steps, table_dev, table_steps, stream);
 }
 
 extern "C" int nmf_odor_intensity(nmf_batch* b, const int32_t* sensor_seg_dev, const float* sensor_rel_dev, int n_sensors,
@@ -1567,3 +1552,4 @@ extern "C" int nmf_debug_eye_stats(unsigned long long* out) {
   return 0;
 }
 #endif
+#endif  // NMF_DEVMEM_CHECK

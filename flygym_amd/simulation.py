@@ -160,11 +160,7 @@ class HIPSimulation:
     def field(self, name: str):
         """Zero-copy torch view ``(n_worlds, width)`` of an engine array (aliases device state)."""
         if name not in self._views:
-            width = ctypes.c_int32(0)
-            ptr = self._lib.nmf_field_ptr(self._batch_h, _native.FIELDS[name], ctypes.byref(width))
-            if not ptr:
-                raise _native.NativeError(self._lib.nmf_last_error().decode())
-            view = _tensor_from_ptr(self._torch, ptr, (self.n_worlds, max(width.value, 0)), self.device)
+            view = _field_view(self, self._lib.nmf_field_ptr, self._batch_h, _native.FIELDS[name])
             if name in _native.INT_FIELDS:       # integer counters behind the float-typed field pointer (include/nmf.h)
                 view = view.view(self._torch.int32)
             self._views[name] = view
@@ -619,6 +615,16 @@ def _tensor_from_ptr(torch, ptr: int, shape, device, typestr: str = "<f4"):
     }
     t = torch.as_tensor(h, device=device)
     return t[:n].reshape(shape)
+
+
+def _field_view(sim, field_ptr, handle, which: int, typestr: str = "<f4"):
+    """Zero-copy view ``(n_worlds, width)`` of field ``which`` of a native handle on ``sim``'s device; ``field_ptr`` is the handle's
+    ``nmf_*_field_ptr`` entry point."""
+    width = ctypes.c_int32(0)
+    ptr = field_ptr(handle, which, ctypes.byref(width))
+    if not ptr:
+        raise _native.NativeError(_native.lib().nmf_last_error().decode())
+    return _tensor_from_ptr(sim._torch, ptr, (sim.n_worlds, max(width.value, 0)), sim.device, typestr)
 
 
 class _DataView:

@@ -426,6 +426,59 @@ def test_refusals_leave_the_state_untouched(torch_mod):
     assert hyb.retraction is None and hyb.rule_flags is None
 
 
+def test_refused_creations_leak_nothing_and_leave_the_controller_usable(torch_mod):
+    """Two worlds of the LEGS_ONLY model.  32 rounds of one refused call per handle type — a camera plan with a capsule segment out of
+    range, a CPG with a leg index outside 0..5, ``nmf_cpg_hybrid_enable`` with a tip segment out of range on a live controller — each
+    rejected by the host checks before any kernel runs.  Afterwards the device has no less free memory than before the rounds, to
+    within the one allocation granule that a 16-byte ``torch.empty`` moves ``mem_get_info`` by here, and the live controller's next
+    4 steps are a fresh controller's bit for bit."""
+    torch = torch_mod
+    from flygym_amd import _native
+    from flygym_amd.controllers import TurningCPG
+    from flygym_amd.rendering import HIPBatchRenderer
+
+    lib = _native.lib()
+    sim, fly = _batch(n=2)
+    # one create / destroy of each handle type first: the runtime's pools are populated before the measurement
+    cam = HIPBatchRenderer(sim, "trackcam", worlds=[0]); cam.close()
+    hyb = _hybrid(sim, fly, adhesion=None); hyb.close()
+    live = TurningCPG(sim, fly.name, table_steps=TABLE_STEPS)
+    torch.cuda.synchronize()
+    free = lambda: torch.cuda.mem_get_info(sim.device)[0]
+    start = free()
+    probe = torch.empty(16, dtype=torch.uint8, device=sim.device)
+    granule = start - free()
+    before = free()
+
+    nseg = sim.model.nseg
+    one = np.zeros(1, dtype=np.int32)
+    seg = np.asarray([nseg], dtype=np.int32); geom = np.ones(7, dtype=np.float32); rgb = np.zeros(3, dtype=np.uint8)
+    cyc = np.ascontiguousarray(live.cycle, dtype=np.float32)
+    bad_legs = np.ascontiguousarray(live.leg_of_dof, dtype=np.int32); bad_legs[7] = 6
+    bad_tips = hyb.tip_seg.copy(); bad_tips[4] = nseg
+    for _ in range(32):
+        assert not lib.nmf_camera_plan_create(sim._batch_h, ctypes.byref(cam._params), 1, one.ctypes.data, 1, seg.ctypes.data,
+                                              geom.ctypes.data, rgb.ctypes.data, 1)
+        assert b"capsule segment out of range" in lib.nmf_last_error()
+        assert not lib.nmf_cpg_create(sim._batch_h, ctypes.byref(live._params), cyc.ctypes.data, bad_legs.ctypes.data, None)
+        assert b"leg_of_col[7]" in lib.nmf_last_error()
+        assert lib.nmf_cpg_hybrid_enable(live._h, ctypes.byref(hyb._hybrid_params), hyb.corr.ctypes.data, hyb.swing.ctypes.data,
+                                         hyb.root_seg, bad_tips.ctypes.data) != 0
+        assert b"tip_seg[4]" in lib.nmf_last_error()
+    torch.cuda.synchronize()
+    after = free()
+    print(f"free device memory: {before} B before the refused calls, {after} B after; allocation granule {granule} B")
+    assert after >= before - granule, (before, after, granule)
+    del probe
+
+    fresh = TurningCPG(sim, fly.name, table_steps=TABLE_STEPS)
+    rows, want = live.advance(4)[:, :4], fresh.advance(4)[:, :4]
+    torch.cuda.synchronize()
+    assert torch.equal(rows, want) and bool(torch.isfinite(rows).all()) and bool((rows != 0).any())
+    assert torch.equal(live.phase, fresh.phase) and torch.equal(live.magnitude, fresh.magnitude)
+    live.close(); fresh.close()
+
+
 def test_closed_loop_on_the_gapped_terrain(torch_mod):
     """21 flies on the gapped terrain, 100 ticks of 20 steps through ``HybridTurningCPG.step``: everything stays finite,
     0 <= rho, sigma <= cap, and the flags of every tick are those the specification decides from the views read before the tick.
