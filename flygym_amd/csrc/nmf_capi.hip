@@ -1542,6 +1542,16 @@ extern "C" int nmf_debug_stage_cycles(unsigned long long* out, int n, int reset)
   if (reset) { unsigned long long z[NMF_NSTAGE] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(nmf::g_stage_cycles), z, sizeof(z)); }
   return 0;
 }
+// diagnostic build only: the shared-prefix histogram of the contact-space solve's later eliminations (nmf_step_diag.h)
+// (n: the words `out` holds; the call fails unless that is the histogram's size, returned when out is null)
+extern "C" int nmf_debug_resume_hist(unsigned long long* out, int n, int reset) {
+  if (!out) return NMF_RESUME_ROWS * 65;
+  if (n != NMF_RESUME_ROWS * 65) return -1;
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(nmf::g_resume_hist), sizeof(unsigned long long) * NMF_RESUME_ROWS * 65) != hipSuccess) return -1;
+  if (reset) { static unsigned long long z[NMF_RESUME_ROWS * 65] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(nmf::g_resume_hist), z, sizeof(z)); }
+  return 0;
+}
 #endif
 #ifdef NMF_EYE_STATS
 extern "C" int nmf_debug_eye_stats(unsigned long long* out) {

@@ -38,6 +38,7 @@
 // registers — is ordered so that only the blocks a step needs are ever fetched.
 // Development switch: NMF_DUAL_DEBUG (per-iteration printf of world 0).
 #pragma once
+#include "nmf_dual_chain.h"
 
 namespace nmf {
 
@@ -102,50 +103,17 @@ __device__ __forceinline__ float quad_sum(float v) {
   v += NMF_DPP(v, 0x4E);
   return v;
 }
+// How many leading pivots a step's later eliminations may take over from the one before (0: every elimination starts at ordinal
+// 0).  -DNMF_DUAL_NO_RESUME: none, for comparing the two bit for bit; direction pivots (-DNMF_DUAL_DIRS) change a contact's
+// columns and right-hand side with its pivot set, so nothing is shared there.
+#if defined(NMF_DUAL_NO_RESUME) || defined(NMF_DUAL_DIRS)
+template <class TP> inline constexpr int kDualKeep = 0;
+#else
+template <class TP> inline constexpr int kDualKeep = kDualS<TP> ? 16 : 0;
+#endif
 constexpr int dual_root_axis(int i) { return i < 3 ? 2 - i : 8 - i; }     // elimination order of the root (aba_solve)
 
-// Gauss-Jordan elimination of [R + A | b], left-looking, unrolled by pivot ORDINAL (the p-th active row, whatever its index):
-// only the code of the pivots a step really has is ever fetched.  Lane i keeps cq[p] = (column of pivot p, row i) / sqrt(d_p),
-// zero on the pivot's own row; the pivot row's entry at a later pivot column kk is that column's entry of row kk by symmetry
-// of the not-yet-eliminated block — v_readlane(cq[q], kk) — so column kk of the current matrix is
-//   A[.][kk] - sum_{q < p} cq[q] * cq[q](lane kk)      (two chains: the sum is a dependent sequence of multiply-adds).
-// A's column kk is four reads of G (DualCol), requested a pivot ahead.  On return b holds the eliminated right-hand
-// side, diag the pivot of the lane's own row (active rows).
-template <int PMAX>
-__device__ __forceinline__ void dual_eliminate(unsigned long long rem, const DualCol& dc, float R, int lane, float& b, float& diag) {
-  float cq[PMAX];
-  auto first_of = [](unsigned long long r) { return __builtin_amdgcn_readfirstlane(max(__ffsll((long long)r) - 1, 0)); };      // (0 for an empty set: a harmless fetch)
-  int kk_next = first_of(rem);
-  DualCol::Raw an = dc.fetch(kk_next);
-  // (Round 6, measured and dropped: the two rows of a pyramid pair read the same four entries of G and differ in the sign of mu
-  // only — skipping the reads and their address arithmetic when the next pivot is this one's pair mate costs a scalar branch per
-  // pivot in front of the reads that are meant to be in flight early: 59.9 -> 59.0 M.)
-#define NMF_DUAL_PIVOT(P)                                                                                   \
-  if constexpr (P < PMAX) {                                                                                 \
-    if (rem == 0ull) return;                                                                                \
-    const int kk = kk_next;                                                                                 \
-    rem &= rem - 1ull;                                                                                      \
-    float col = dc.value(an) + (lane == kk ? R : 0.f);                                                      \
-    kk_next = first_of(rem);                                                                                \
-    an = dc.fetch(kk_next);                                                                                 \
-    __builtin_amdgcn_sched_barrier(0);      /* the next column's reads are in flight while this pivot's chain runs */ \
-    { float c1 = 0.f;                                                                                       \
-      _Pragma("unroll") for (int q = 0; q + 1 < P; q += 2) {                                                \
-        col = fmaf(-cq[q], readlane_f(cq[q], kk), col); c1 = fmaf(-cq[q + 1], readlane_f(cq[q + 1], kk), c1); } \
-      if constexpr ((P) % 2) col = fmaf(-cq[P - 1], readlane_f(cq[P - 1], kk), col);                        \
-      col += c1; }                                                                                          \
-    const float d = readlane_f(col, kk);                                                                    \
-    const float rs = __builtin_amdgcn_rsqf(d);                                                              \
-    diag = lane == kk ? d : diag;                                                                           \
-    const float cp = lane == kk ? 0.f : col * rs;                                                           \
-    b = fmaf(-cp, readlane_f(b, kk) * rs, b);                                                               \
-    cq[P] = cp;                                                                                             \
-  }
-#define NMF_DUAL_PIVOT8(P) NMF_DUAL_PIVOT(P) NMF_DUAL_PIVOT(P + 1) NMF_DUAL_PIVOT(P + 2) NMF_DUAL_PIVOT(P + 3) NMF_DUAL_PIVOT(P + 4) NMF_DUAL_PIVOT(P + 5) NMF_DUAL_PIVOT(P + 6) NMF_DUAL_PIVOT(P + 7)
-  NMF_DUAL_PIVOT8(0) NMF_DUAL_PIVOT8(8) NMF_DUAL_PIVOT8(16) NMF_DUAL_PIVOT8(24) NMF_DUAL_PIVOT8(32) NMF_DUAL_PIVOT8(40) NMF_DUAL_PIVOT8(48) NMF_DUAL_PIVOT8(56)
-#undef NMF_DUAL_PIVOT8
-#undef NMF_DUAL_PIVOT
-}
+// (dual_eliminate, the elimination itself: nmf_dual_chain.h — a header the host compiles too, scripts/micro/dual_resume_check.cpp)
 
 // What the primal loop needs and a contact-space solve overwrote — the inertias (star kernels: G lies on Ib; Isym holds the same
 // numbers) and the twists of the unconstrained acceleration in T.  Its own function: a rejected solve is one in ten thousand, and
@@ -408,6 +376,14 @@ __device__ __forceinline__ int dual_solve(FlyLds<TP>& s, const GModel& m, int la
   unsigned long long viol_last = 0ull;
   unsigned long long mask_p = ~0ull, mask_pp = ~0ull;      // the pivot sets of the last two eliminations (none yet)
   unsigned long long mask = guessed ? __ballot(on && (hist_nib ? ((hist_nib >> k) & 1) != 0 : jar < 0.f)) : __ballot(on && jar < 0.f);
+#ifdef NMF_STAGE_PROFILE
+  unsigned long long mask_e_diag = 0ull;
+#endif
+  // what one elimination of this step leaves for the next (dual_eliminate): the first KEEP multipliers, b every kDualSnap ordinals,
+  // the pivots, its pivot set.  KEEP is what the registers carry across the line search without a spill (kDualKeep).
+  constexpr int KEEP = kDualKeep<TP>;
+  float cq[4 * NC], bsnap[KEEP / kDualSnap + 1], diag = 1.f;
+  [[maybe_unused]] unsigned long long mask_kept = 0ull;
   for (int iter = 0; iter < m.max_iter; ++iter) {
     iters = iter + 1;
     // Gauss-Jordan on [R + A | j0]: pivots = active rows in index order, every row takes part
@@ -428,7 +404,7 @@ __device__ __forceinline__ int dual_solve(FlyLds<TP>& s, const GModel& m, int la
     // Build with -DNMF_DUAL_DIRS to get it (the code below is the same either way: with `fullc` false every contact keeps its rows).
     const bool fullc = false;
 #endif
-    float b, diag = 1.f, R_e = R;
+    float b, R_e = R;
     unsigned long long mask_e = mask;
     {
       const float q0 = NMF_DPP(j0, 0x00), q1 = NMF_DPP(j0, 0x55), q2 = NMF_DPP(j0, 0xAA), q3 = NMF_DPP(j0, 0xFF);
@@ -440,7 +416,20 @@ __device__ __forceinline__ int dual_solve(FlyLds<TP>& s, const GModel& m, int la
       dcol.beta = fullc ? ((k == 1 || k == 2) ? 1.f : 0.f) : smu;
       mask_e = __ballot(fullc ? k < 3 : (bool)((mask >> lane) & 1ull));
     }
-    dual_eliminate<4 * NC>(mask_e, dcol, R_e, lane, b, diag);
+    // where this elimination takes up the last one's work (dual_eliminate): the pivots below the first row the two sets differ in
+    int start = 0;
+    if constexpr (KEEP > 0) {
+      start = iter > 0 ? __builtin_amdgcn_readfirstlane(dual_resume_ordinal<KEEP>(mask_e, mask_kept)) : 0;
+      mask_kept = mask_e;
+    }
+    diag = start > 0 ? diag : 1.f;
+    dual_eliminate<4 * NC, KEEP>(mask_e, dcol, R_e, lane, b, diag, cq, bsnap, start);
+#ifdef NMF_STAGE_PROFILE
+    // (diagnostic build: how many leading pivots this elimination repeats from the one before — the first differing row bounds them)
+    if (iter == 0) RESUME_HIST(NMF_RESUME_ROWS - 1, 0);
+    else { const unsigned long long df = mask_e ^ mask_e_diag; RESUME_HIST(__popcll(mask_e), __popcll(mask_e & (df ? (df & (0ull - df)) - 1ull : ~0ull))); }
+    mask_e_diag = mask_e;
+#endif
     const bool act = (mask >> lane) & 1ull;
     const bool piv = (mask_e >> lane) & 1ull;
     const float x = piv ? -b * __builtin_amdgcn_rcpf(diag) : 0.f;               // phi* on direction lanes, lambda* on pivot rows

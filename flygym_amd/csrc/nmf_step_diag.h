@@ -29,7 +29,13 @@ struct StageClock { unsigned long long last; unsigned long long* acc; };
 #define SUB_COUNT(k, n) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_stage_cycles[k] += (unsigned long long)(n); } while (0)
 #define SUBH_T0() unsigned long long subh_t_ = clock64()
 #define SUBH(k) do { if (blockIdx.x == 0 && threadIdx.x == 0) { unsigned long long t_ = clock64(); g_stage_cycles[k] += t_ - subh_t_; subh_t_ = clock64(); } } while (0)
+// (contact-space solve, every workgroup) eliminations beyond a step's first: [pivots of the elimination][leading pivots, in row
+// order, that it shares with the elimination before it]; row 65: [0] = first eliminations (= solves).  scripts/resume_prefix.py
+#define NMF_RESUME_ROWS 66
+__device__ unsigned long long g_resume_hist[NMF_RESUME_ROWS][65];
+#define RESUME_HIST(n, k) do { if (threadIdx.x == 0) atomicAdd(&g_resume_hist[n][k], 1ull); } while (0)
 #else
+#define RESUME_HIST(n, k)
 #define SUBH_T0()
 #define SUBH(k)
 #define SUB_T0()
