@@ -23,6 +23,7 @@
 #include "nmf_camera.hip"
 #include "nmf_replay.hip"
 #include "nmf_cpg.hip"
+#include "nmf_skeleton.h"      // nmf_model, the blob parser, classify_skeleton
 #endif
 
 namespace {
@@ -91,20 +92,6 @@ struct DevMem {
 #ifndef NMF_DEVMEM_CHECK      // (to the end of the file)
 namespace {
 
-struct BlobEntry {
-  char name[32];
-  uint32_t dtype, ndim;
-  int64_t shape[4];
-  int64_t offset, nbytes;
-};
-
-struct HostArray {
-  std::vector<float> f;
-  std::vector<int32_t> i;
-  bool is_int = false;
-  int64_t count = 0;
-};
-
 // The body of a *_create entry point: `fill` builds the fresh handle `h` with its device current.  If it fails the handle is
 // destroyed, the error text stays, and the caller gets null.
 template <class H, class Fill>
@@ -120,17 +107,6 @@ H* build_or_destroy(int device, const char* who, H* h, void (*destroy)(H*), Fill
 }
 
 }  // namespace
-
-struct nmf_model {
-  std::vector<uint8_t> blob;
-  std::vector<std::pair<std::string, HostArray>> arrays;
-  int nq = 0, nv = 0, nu = 0, nb = 0, nseg = 0, ng = 0, nsite = 0, nsensor = 0, max_iter = 100;
-  int star[4] = {0, 0, 0, 0};
-  const HostArray* find(const char* name) const {
-    for (auto& kv : arrays) if (kv.first == name) return &kv.second;
-    return nullptr;
-  }
-};
 
 // Visit plan of the eye renderer (nmf_eye_plan_create): everything the kernel reads that depends on the id map, the lens and the
 // ommatidia types — with its OWN device copies of the id map, the retina run plan, the pale flags and the normalisation, so that
@@ -191,54 +167,9 @@ extern "C" const char* nmf_last_error(void) { return g_err.c_str(); }
 
 extern "C" nmf_model* nmf_model_create(const void* blob, size_t nbytes) {
   g_err.clear();
-  if (!blob || nbytes < 16 || memcmp(blob, "NMFMODEL", 8) != 0) { fail("nmf_model_create: not an NMFMODEL blob"); return nullptr; }
-  auto* m = new nmf_model();
-  m->blob.assign((const uint8_t*)blob, (const uint8_t*)blob + nbytes);
-  uint32_t version, n;
-  memcpy(&version, m->blob.data() + 8, 4);
-  memcpy(&n, m->blob.data() + 12, 4);
-  if (version != 4) { delete m; fail("nmf_model_create: unsupported blob version (this library reads NMFMODEL v4)"); return nullptr; }
-  if ((uint64_t)n > (nbytes - 16) / sizeof(BlobEntry)) { delete m; fail("nmf_model_create: entry table does not fit the blob"); return nullptr; }
-  const BlobEntry* e = (const BlobEntry*)(m->blob.data() + 16);
-  for (uint32_t k = 0; k < n; ++k) {
-    HostArray a;
-    int64_t c = 1;
-    bool bad = e[k].ndim > 4 || e[k].dtype > 1 || e[k].offset < 0 || e[k].nbytes < 0;
-    for (uint32_t d = 0; !bad && d < e[k].ndim; ++d) {
-      bad = e[k].shape[d] < 0 || (e[k].shape[d] > 0 && c > (int64_t)nbytes / e[k].shape[d]);
-      c *= e[k].shape[d];
-    }
-    a.count = c;
-    const int64_t elem = e[k].dtype == 0 ? 8 : 4;
-    if (bad || (uint64_t)e[k].offset > nbytes || (uint64_t)e[k].nbytes > nbytes - (uint64_t)e[k].offset || c * elem > e[k].nbytes) {
-      delete m; fail("nmf_model_create: truncated or malformed blob entry"); return nullptr;
-    }
-    if (e[k].dtype == 0) {
-      const double* src = (const double*)(m->blob.data() + e[k].offset);
-      a.f.resize((size_t)c);
-      for (int64_t i = 0; i < c; ++i) a.f[(size_t)i] = (float)src[i];
-    } else {
-      a.is_int = true;
-      a.i.resize((size_t)c);
-      memcpy(a.i.data(), m->blob.data() + e[k].offset, sizeof(int32_t) * (size_t)c);
-    }
-    char nm[33];
-    memcpy(nm, e[k].name, 32); nm[32] = 0;
-    m->arrays.emplace_back(std::string(nm), std::move(a));
-  }
-  auto need = [&](const char* nm) -> const HostArray* {
-    const HostArray* a = m->find(nm);
-    if (!a) fail(std::string("nmf_model_create: blob lacks entry ") + nm);
-    return a;
-  };
-  const HostArray *bp = need("body_parent"), *db = need("dof_body"), *at = need("act_type"), *sb = need("seg_body"),
-                  *gb = need("geom_body"), *si = need("site_body"), *ns = need("n_sensor"), *os = need("opt_solver"),
-                  *star = need("star");
-  if (!bp || !db || !at || !sb || !gb || !si || !ns || !os || !star) { delete m; return nullptr; }
-  m->nb = (int)bp->count; m->nv = (int)db->count; m->nq = m->nv + 1; m->nu = (int)at->count;
-  m->nseg = (int)sb->count; m->ng = (int)gb->count; m->nsite = (int)si->count;
-  m->nsensor = ns->i[0]; m->max_iter = os->i[0];
-  for (int k = 0; k < 4; ++k) m->star[k] = star->i[(size_t)k];
+  std::string err;
+  nmf_model* m = parse_model(blob, nbytes, err);
+  if (!m) fail(err);
   return m;
 }
 
@@ -310,28 +241,13 @@ void alloc_field(nmf_batch* b, int field, int width, float** out) {
 template <class T> struct TopoTag { using type = T; };
 
 // The kernel family of a batch (nmf_batch::topo) as its topology type: calls f(TopoTag<TP>{}), false for a family this build
-// left out (NMF_TOPO_MASK).  The one place the host side lists the families.
+// left out (NMF_TOPO_MASK).  Generated from the family list, NMF_FAMILIES (nmf_families.h).
 template <class F>
 bool with_topo(int topo, F&& f) {
   switch (topo) {
-#if NMF_HAS_TOPO(0)
-    case 0: f(TopoTag<nmf::FlyTopo>{}); return true;
-#endif
-#if NMF_HAS_TOPO(1)
-    case 1: f(TopoTag<nmf::FlyTopoActive>{}); return true;
-#endif
-#if NMF_HAS_TOPO(2)
-    case 2: f(TopoTag<nmf::TreeTopoSmall>{}); return true;
-#endif
-#if NMF_HAS_TOPO(3)
-    case 3: f(TopoTag<nmf::TreeTopo>{}); return true;
-#endif
-#if NMF_HAS_TOPO(4)
-    case 4: f(TopoTag<nmf::FlyTopoBio>{}); return true;
-#endif
-#if NMF_HAS_TOPO(5)
-    case 5: f(TopoTag<nmf::FlyTopoAll>{}); return true;
-#endif
+#define NMF_CASE(k, TP, ...) NMF_IF_TOPO_##k(case k: f(TopoTag<nmf::TP>{}); return true;)
+    NMF_FAMILIES(NMF_CASE)
+#undef NMF_CASE
     default: return false;
   }
 }
@@ -453,92 +369,10 @@ Options read_options(const nmf_batch_options& in) {
   return o;
 }
 
-// The skeleton's kernel family and, for the families with tree sweeps, the tree tables in breadth-first order
-struct Skeleton {
-  int topo = -1;
-  std::vector<int> tree_body, child_start, child_count, lvl_start;    // lvl_start: starts of levels 0..maxd and the end
-};
-
-int classify_skeleton(const nmf_model* model, Skeleton& sk) {
-  int& topo = sk.topo;
-  if (model->star[0] == 1 && model->star[1] == 6 && model->star[2] == 11 && model->star[3] == 8) topo = 0;
-  if (model->star[0] == 1 && model->star[1] == 6 && model->star[2] == 7 && model->star[3] == 4) topo = 1;
-  if (topo >= 0) {  // the chain-star kernels hard-wire the per-leg hinge layout (and 48 controls); anything else takes the tree kernel
-    const HostArray* dn = model->find("body_dofnum");
-    const int pat0[8] = {3, 2, 1, 1, 1, 1, 1, 1}, pat1[4] = {3, 2, 1, 1};
-    const int* pat = topo == 0 ? pat0 : pat1;
-    const int nbl = topo == 0 ? 8 : 4;
-    bool ok = dn && dn->is_int && (int)dn->i.size() == 1 + 6 * nbl && dn->i[0] == 6;
-    for (int b = 1; ok && b < 1 + 6 * nbl; ++b) ok = dn->i[(size_t)b] == pat[(b - 1) % nbl];
-    if (!ok || model->nu > nmf::kMaxCtrl) topo = -1;
-  }
-  // the full-body skeletons (ALL_BIOLOGICAL, ALL_POSSIBLE): six identical leg chains at the END of the body order, the
-  // rest of the body (20 bodies, 60 dofs) between the root and the legs -> hybrid kernels (legs unrolled, rest as a tree)
-  std::vector<char> in_tree;          // bodies the tree tables cover (hybrid: root + rest; tree kernels: all)
-  if (topo < 0) {
-    const HostArray* bp = model->find("body_parent");
-    const HostArray* dn = model->find("body_dofnum");
-    const int patB[8] = {3, 2, 1, 1, 1, 1, 1, 1}, patA[8] = {3, 3, 3, 3, 3, 3, 3, 3};
-    for (int cand = 4; cand <= 5 && topo < 0 && bp && dn; ++cand) {
-      const int* pat = cand == 4 ? patB : patA;
-      const int nb = model->nb, lb0 = 21, want_nv = cand == 4 ? 132 : 210;
-      bool ok = nb == 69 && model->nv == want_nv && (int)dn->i.size() == nb && dn->i[0] == 6 && model->nu <= (cand == 4 ? nmf::FlyTopoBio::kCtrl : nmf::FlyTopoAll::kCtrl);
-      int rest_v = 0;
-      for (int bb = 1; ok && bb < lb0; ++bb) { rest_v += dn->i[(size_t)bb]; ok = bp->i[(size_t)bb] >= 0 && bp->i[(size_t)bb] < lb0 && bp->i[(size_t)bb] < bb; }
-      ok = ok && rest_v == 60;
-      for (int bb = lb0; ok && bb < nb; ++bb) {
-        const int l = (bb - lb0) % 8;
-        ok = dn->i[(size_t)bb] == pat[l] && bp->i[(size_t)bb] == (l == 0 ? 0 : bb - 1);
-      }
-      if (ok) { topo = cand; in_tree.assign((size_t)nb, 0); for (int bb = 0; bb < lb0; ++bb) in_tree[(size_t)bb] = 1; }
-    }
-  }
-  // anything else (custom skeletons): the general-tree kernel, up to 72 bodies / 216 dofs
-  std::vector<int> &tree_body = sk.tree_body, &child_start = sk.child_start, &child_count = sk.child_count, &lvl_start = sk.lvl_start;
-  if (topo < 0 || topo >= 4) {
-    if (topo < 0) topo = model->nv <= nmf::TreeTopoSmall::NV && model->nu <= nmf::TreeTopoSmall::kCtrl ? 2 : 3;
-    const HostArray* bp = model->find("body_parent");
-    const HostArray* dn = model->find("body_dofnum");
-    const HostArray* gb = model->find("geom_body");
-    if (!bp || !dn || !gb || model->nb > nmf::TreeTopo::NB || model->nv > nmf::TreeTopo::NV || dn->i.empty() || dn->i[0] != 6)
-      return fail("nmf_batch_create: the general-tree kernel takes a free-floating root and up to 72 bodies / 216 dofs");
-    const int nb = model->nb;
-    if (in_tree.empty()) in_tree.assign((size_t)nb, 1);
-    for (int bb = 1; bb < nb; ++bb)
-      if (bp->i[(size_t)bb] < 0 || bp->i[(size_t)bb] >= bb) return fail("nmf_batch_create: bodies must be ordered parents first");
-    for (size_t g = 1; g < gb->i.size(); ++g)
-      if (gb->i[g] < gb->i[g - 1]) return fail("nmf_batch_create: contact geoms must be ordered by body");
-    // breadth-first order: level by level, the children of a body contiguous
-    std::vector<int> depth((size_t)nb, 0);
-    int maxd = 0;
-    for (int bb = 1; bb < nb; ++bb) {
-      depth[(size_t)bb] = depth[(size_t)bp->i[(size_t)bb]] + 1;
-      if (in_tree[(size_t)bb]) maxd = std::max(maxd, depth[(size_t)bb]);
-    }
-    if (maxd + 2 > 18) return fail("nmf_batch_create: kinematic tree deeper than 16 levels");
-    tree_body.push_back(0); lvl_start.push_back(0);
-    child_start.assign((size_t)nb, 0); child_count.assign((size_t)nb, 0);
-    for (int lv = 0; lv <= maxd; ++lv) {
-      const int k0 = lvl_start[(size_t)lv], k1 = (int)tree_body.size();
-      lvl_start.push_back(k1);
-      for (int k = k0; k < k1; ++k) {
-        const int par = tree_body[(size_t)k];
-        child_start[(size_t)par] = (int)tree_body.size();
-        for (int bb = 1; bb < nb; ++bb) if (bp->i[(size_t)bb] == par && in_tree[(size_t)bb]) { tree_body.push_back(bb); child_count[(size_t)par]++; }
-      }
-      if (k1 - k0 > nmf::kWave) return fail("nmf_batch_create: more than 64 bodies on one tree level");
-    }
-    // lvl_start has maxd + 2 entries: starts of levels 0..maxd and the end
-  }
-  if (model->ng > 2 * nmf::kWave) return fail("nmf_batch_create: more than 128 contact geoms");
-  if (model->nu > (topo >= 2 ? nmf::TreeTopo::kCtrl : nmf::kMaxCtrl)) return fail("nmf_batch_create: too many actuators (48 for the leg skeletons, 224 otherwise)");
-  return 0;
-}
-
 // DevModel: the model's scalars and arrays, the tree tables and the solver option bits, uploaded to b->dm_dev
 int fill_model(nmf_batch* b, const Skeleton& sk, const Options& opt) {
   const nmf_model* model = b->model;
-  const int topo = sk.topo;
+  const nmf::Family& fam = nmf::family(sk.topo);
   const std::vector<int> &tree_body = sk.tree_body, &child_start = sk.child_start, &child_count = sk.child_count, &lvl_start = sk.lvl_start;
   nmf::DevModel& d = b->dm;
   d.nb = model->nb; d.nv = model->nv; d.nq = model->nq; d.nu = model->nu; d.ng = model->ng;
@@ -588,7 +422,7 @@ int fill_model(nmf_batch* b, const Skeleton& sk, const Options& opt) {
   UF(pair_friction); UF(pair_solref); UF(pair_solimp); UF(pair_margin);
 #undef UF
 #undef UI
-  if (topo >= 2) {
+  if (fam.tree_tables()) {
     const HostArray* bp = model->find("body_parent");
     upload(b, bp->i, &d.body_parent);
     upload(b, tree_body, &d.tree_body);
@@ -597,24 +431,8 @@ int fill_model(nmf_batch* b, const Skeleton& sk, const Options& opt) {
     d.tree_nlevel = (int)lvl_start.size() - 1;
     for (size_t k = 0; k < 18; ++k) d.tree_lvl_start[k] = k < lvl_start.size() ? lvl_start[k] : (int)tree_body.size();
     d.rest_fast = 0; d.rest_pack = nullptr;
-    if (topo >= 4) {
-      const HostArray* dn = model->find("body_dofnum");
-      const HostArray* da = model->find("body_dofadr");
-      const int nl = (int)lvl_start.size() - 2;                 // levels below the root
-      bool fast = da && nl <= nmf::kRestLevels && !opt.rest_slow;
-      std::vector<int> pack((size_t)nmf::kRestLevels * 16, -1);
-      for (int lv = 1; fast && lv <= nl; ++lv) {
-        const int k0 = lvl_start[(size_t)lv], k1 = lvl_start[(size_t)lv + 1];
-        fast = k1 - k0 <= 8;
-        for (int k = k0; fast && k < k1; ++k) {
-          const int bb = tree_body[(size_t)k];
-          fast = dn->i[(size_t)bb] == 3 && da->i[(size_t)bb] < 256 && child_count[(size_t)bb] < 256 && child_start[(size_t)bb] < 256;
-          pack[(size_t)((lv - 1) * 8 + (k - k0)) * 2] = bb | (bp->i[(size_t)bb] << 8) | (da->i[(size_t)bb] << 16) | (child_count[(size_t)bb] << 24);
-          pack[(size_t)((lv - 1) * 8 + (k - k0)) * 2 + 1] = child_start[(size_t)bb] | (k << 8);
-        }
-      }
-      if (fast) { d.rest_fast = 1; upload(b, pack, &d.rest_pack); }
-    }
+    std::vector<int> pack;
+    if (fam.hybrid() && !opt.rest_slow && rest_pack_words(model, sk, pack)) { d.rest_fast = 1; upload(b, pack, &d.rest_pack); }
   } else {
     d.body_parent = d.tree_body = d.tree_child_start = d.tree_child_count = nullptr; d.tree_nlevel = 0; d.rest_fast = 0; d.rest_pack = nullptr;
   }
@@ -648,8 +466,8 @@ int alloc_state(nmf_batch* b) {
   alloc_dev(b, n_worlds * nmf::kActHistWords, &st.act_hist);
   st.stats_sum = reinterpret_cast<unsigned int*>(stats_sum);
   st.dual_scratch = nullptr;
-  // ALL_POSSIBLE: the contact-space solve's leg factors live in HBM, one block per workgroup of a launch (<= n_worlds)
-  if (b->topo == 5) alloc_dev(b, n_worlds * nmf::kDualScratchFloats, &st.dual_scratch);
+  // kDualGlob (ALL_POSSIBLE): the contact-space solve's leg factors live in HBM, one block per workgroup of a launch (<= n_worlds)
+  with_topo(b->topo, [&](auto tag) { if (nmf::kDualGlob<typename decltype(tag)::type>) alloc_dev(b, n_worlds * nmf::kDualScratchFloats, &st.dual_scratch); });
   st.noslip_buf = nullptr;
   // CPU flavour: scratch of the primal path's noslip pass (157 KB per world)
   if (b->dm.noslip_iter > 0) alloc_dev(b, n_worlds * nmf::kNoslipFloats, &st.noslip_buf);
@@ -666,12 +484,8 @@ void set_schedule(nmf_batch* b, const Options& opt) {
   if (opt.order) b->order_policy = opt.order == 1 ? 0 : opt.order == 2 ? 1 : opt.order == 3 ? 2 : opt.order == 4 ? -1 : 3;
   if (opt.order_every > 0) b->order_every = opt.order_every;
   if (opt.max_chunks > 0) b->max_chunks = std::max(1, std::min(16, opt.max_chunks));
-  // (flat ground, leg-chain skeleton: a world's cost varies least and a step is cheapest against the hand-over — fewer, longer
-  // chunks; terrains and the full-body skeletons keep the halving plan: blocks 34.2 vs 32.4 M, ALL_BIOLOGICAL 30.7 vs 30.2 M)
-  // (and launches of more than 64 steps: 250-step launches 56.1 M halving, 54.5 M with 1.6)
-  // (round 5, one contact-space solve for every walking step: 1.5 / 1.6 / 1.7 / 1.8 / 2.0 = 56.7 / 56.6 / 56.7 / 56.6 / 55.8 M on 20-step
-  // launches, 58.7 / 58.9 / 59.2 / 59.0 / 58.9 M on 50-step ones)
-  b->chunk_div = (b->dm.terrain_type == 0 && b->topo < 2) ? 1.7 : 2.0;
+  // (the family's own divisor on flat ground — NMF_FAMILIES, nmf_families.h —, halving chunks over a terrain)
+  b->chunk_div = b->dm.terrain_type == 0 ? nmf::family(b->topo).chunk_div : 2.0;
   b->chunk_div_short = true;
   if (opt.chunk_div > 0.0) { b->chunk_div = opt.chunk_div; b->chunk_div_short = false; }
   if (opt.min_chunk_steps > 0) b->min_chunk_steps = opt.min_chunk_steps;
@@ -681,11 +495,10 @@ void set_schedule(nmf_batch* b, const Options& opt) {
 }
 
 // The stepping kernel and its residency: flies (= single-wave workgroups) a CU holds at once, asked of the runtime for the
-// kernel this batch will launch (LDS- or register-limited, whichever binds); fallback = the LDS-limited figures of the
-// shipped build
+// kernel this batch will launch (LDS- or register-limited, whichever binds); fallback = the family's figure in NMF_FAMILIES
 int pick_kernel(nmf_batch* b, const Options& opt) {
   const int topo = b->topo, device = b->mem.device;
-  int per_cu = topo < 2 ? 8 : (topo == 2 ? 4 : (topo == 3 ? 3 : (topo == 4 ? 8 : 5)));
+  int per_cu = nmf::family(topo).per_cu;
   const bool weld = b->dm.weld_active != 0, terrain = b->dm.terrain_type != 0;
   if (weld && terrain) return fail("nmf_batch_create: a tethered world has no terrain");
   const void* fn = step_kernel(topo, weld, terrain);
@@ -732,7 +545,7 @@ extern "C" nmf_batch* nmf_batch_create_ex(const nmf_model* model, int n_worlds, 
   if (!model) { fail("nmf_batch_create: null model"); return nullptr; }
   if (n_worlds <= 0) { fail("nmf_batch_create: n_worlds must be positive"); return nullptr; }
   Skeleton sk;
-  if (classify_skeleton(model, sk) != 0) return nullptr;
+  if (const char* why = classify_skeleton(model, sk)) { fail(why); return nullptr; }
   DeviceGuard guard(device);            // allocations and the first reset run on `device`; the caller's device comes back on return
   if (guard.err != hipSuccess) { fail("nmf_batch_create: hipSetDevice failed (no MI355X visible?)"); return nullptr; }
   const Options opt = read_options(in);

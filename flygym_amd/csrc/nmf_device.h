@@ -11,77 +11,16 @@
 #include <type_traits>
 #include <utility>
 
+#include "nmf_families.h"      // topology types, the family list, kWave / kRestLevels / kMaxCtrl
+
 namespace nmf {
 
-constexpr int kWave = 64;
-constexpr int kRestLevels = 6;   // levels below the root the fast passes of the hybrid kernels unroll
 constexpr int kMaxCon = 48;      // contacts per fly kept by the engine (overflow is flagged)
-constexpr int kMaxCtrl = 48;
 constexpr int kActHistWords = 64; // 16 bits per geom, 128 geoms
 constexpr float kMinVal = 1e-15f;
 
 enum { GEOM_CAPSULE = 0, GEOM_HULL = 1 };
 enum { ACT_POSITION = 0, ACT_ADHESION = 1, ACT_MOTOR = 2 };
-
-// Star-of-chains topology: one free root body + NLEG identical serial chains; DOFS... are the
-// hinge counts of the chain's bodies from the root outwards (LEGS_ONLY leg: 3,2,1,1,1,1,1,1).
-// Everything about the chain layout is a compile-time constant so that the leg sweeps unroll
-// completely and never load structure from memory.
-// REST_B / REST_V: bodies / dofs of the "rest" of the fly (head, antennae, proboscis, abdomen, wings, halteres) that sit
-// between the root and the legs in the model's order; they are swept by the general-tree code (nmf_tree.h), the legs by
-// the unrolled chain code.  Leg-only skeletons have no rest.
-template <int REST_B_, int REST_V_, int NLEG_, int... DOFS>
-struct HybridTopo {
-  static constexpr bool kStar = true;
-  static constexpr bool kTerrain = false;   // see Terrain<> below
-  // controls a kernel keeps in LDS: 48 for the leg skeletons, 64 for ALL_BIOLOGICAL (which sits exactly on its LDS budget), 96 for
-  // ALL_POSSIBLE (the default actuated set on it is 72 leg dofs + 6 adhesion); nmf_batch_create sends models with more
-  // actuators to the general-tree kernel, which holds one per dof
-  static constexpr int kCtrl = REST_V_ == 0 ? kMaxCtrl : ((DOFS + ...) > 16 ? 96 : 64);
-  static constexpr int REST_B = REST_B_, REST_V = REST_V_;
-  static constexpr int NLEG = NLEG_;
-  static constexpr int NBL = sizeof...(DOFS);
-  static constexpr int NDL = (DOFS + ...);
-  static constexpr int LB0 = 1 + REST_B_;        // first leg body
-  static constexpr int LD0 = 6 + REST_V_;        // first leg dof
-  static constexpr int kFact0 = 6, kSlot0 = 1;   // the rest dofs / bodies only (tree sweeps); legs and root keep theirs in registers
-  static constexpr int kNFact = REST_V_ > 0 ? REST_V_ : 1, kNSlot = REST_B_ > 0 ? REST_B_ : 1;
-  static constexpr int kTblB = 1 + REST_B_, kTblV = 6 + REST_V_;   // tree tables: root + rest bodies, root + rest dofs
-  static constexpr int NB = LB0 + NLEG_ * NBL;
-  static constexpr int NV = LD0 + NLEG_ * NDL;
-  static constexpr int NQ = NV + 1;
-  static constexpr int dofs(int l) { constexpr int t[] = {DOFS...}; return t[l]; }
-  static constexpr int first_dof(int l) { int a = 0; for (int i = 0; i < l; ++i) a += dofs(i); return a; }
-  static constexpr int lbody(int d) { int a = 0; for (int l = 0; l < NBL; ++l) { a += dofs(l); if (d < a) return l; } return NBL - 1; }
-  static constexpr bool is_last(int d) { return d == first_dof(lbody(d)) + dofs(lbody(d)) - 1; }
-  static constexpr bool is_first(int d) { return d == first_dof(lbody(d)); }
-};
-template <int NLEG_, int... DOFS>
-using Topo = HybridTopo<0, 0, NLEG_, DOFS...>;
-
-// A general kinematic tree (nmf_tree.h): LDS arrays sized for NB_ bodies / NV_ dofs, the actual counts are run-time
-// values of the model.  Two sizes are built: 72 x 144 (ALL_BIOLOGICAL: 69 bodies, 132 dofs; 4 flies per CU) and
-// 72 x 216 (ALL_POSSIBLE: 210 dofs; 3 flies per CU).
-template <int NB_, int NV_>
-struct TreeTopoT {
-  static constexpr bool kStar = false;
-  static constexpr bool kTerrain = false;
-  static constexpr int NB = NB_, NV = NV_, NQ = NV_ + 1;
-  static constexpr int kCtrl = NV_ + 8;      // every dof actuated + adhesion
-  static constexpr int kFact0 = 0, kSlot0 = 1;      // every dof has articulated-body factors, every non-root body a hand-off slot
-  static constexpr int kNFact = NV_, kNSlot = NB_;
-  static constexpr int kTblB = NB_, kTblV = NV_;
-};
-// The same skeleton in a world with a terrain (gapped / blocks / mixed: cells with tops and side faces).  A compile-time
-// property of the kernel: the collision stage against the cells, contacts with their own frames (a side face's normal is
-// horizontal) in every stage that uses the contact frame.  Flat and tethered worlds run the kernels without any of it —
-// the same code, registers and LDS as before the terrain's side faces existed.
-template <class TP>
-struct Terrain : TP {
-  static constexpr bool kTerrain = true;
-};
-using TreeTopo = TreeTopoT<72, 216>;
-using TreeTopoSmall = TreeTopoT<72, 144>;
 
 // The same value, but not one the optimizer can see through: address arithmetic built on it stays where it is written.
 // Used for the once-per-item / once-per-launch paths of the stepping kernel (state hand-over, pure outputs): hoisted out

@@ -295,42 +295,12 @@ __global__ void __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(wave
   STAGE_FLUSH();
 }
 
-using FlyTopo = Topo<6, 3, 2, 1, 1, 1, 1, 1, 1>;   // LEGS_ONLY skeleton: 49 bodies, 72 dofs
-// the full-body skeletons: 20 bodies / 60 dofs of head, antennae, proboscis, abdomen, wings, halteres (tree sweeps) + the
-// six legs (unrolled chain sweeps)
-using FlyTopoBio = HybridTopo<20, 60, 6, 3, 2, 1, 1, 1, 1, 1, 1>;        // ALL_BIOLOGICAL: 69 bodies, 132 dofs
-using FlyTopoAll = HybridTopo<20, 60, 6, 3, 3, 3, 3, 3, 3, 3, 3>;        // ALL_POSSIBLE:   69 bodies, 210 dofs
-using FlyTopoActive = Topo<6, 3, 2, 1, 1>;         // LEGS_ACTIVE_ONLY skeleton: 25 bodies, 48 dofs
-
-#if NMF_HAS_TOPO(0)
-template __global__ void nmf_step_kernel<FlyTopo, false>(const DevModel*, DevState, ReplayArgs, int);
-template __global__ void nmf_step_kernel<FlyTopo, true>(const DevModel*, DevState, ReplayArgs, int);
-template __global__ void nmf_step_kernel<Terrain<FlyTopo>, false>(const DevModel*, DevState, ReplayArgs, int);     // terrain worlds (never tethered)
-#endif
-#if NMF_HAS_TOPO(1)
-template __global__ void nmf_step_kernel<FlyTopoActive, false>(const DevModel*, DevState, ReplayArgs, int);
-template __global__ void nmf_step_kernel<FlyTopoActive, true>(const DevModel*, DevState, ReplayArgs, int);
-template __global__ void nmf_step_kernel<Terrain<FlyTopoActive>, false>(const DevModel*, DevState, ReplayArgs, int);     // terrain worlds (never tethered)
-#endif
-#if NMF_HAS_TOPO(2)
-template __global__ void nmf_step_kernel<TreeTopoSmall, false>(const DevModel*, DevState, ReplayArgs, int);
-template __global__ void nmf_step_kernel<TreeTopoSmall, true>(const DevModel*, DevState, ReplayArgs, int);
-template __global__ void nmf_step_kernel<Terrain<TreeTopoSmall>, false>(const DevModel*, DevState, ReplayArgs, int);     // terrain worlds (never tethered)
-#endif
-#if NMF_HAS_TOPO(3)
-template __global__ void nmf_step_kernel<TreeTopo, false>(const DevModel*, DevState, ReplayArgs, int);
-template __global__ void nmf_step_kernel<TreeTopo, true>(const DevModel*, DevState, ReplayArgs, int);
-template __global__ void nmf_step_kernel<Terrain<TreeTopo>, false>(const DevModel*, DevState, ReplayArgs, int);     // terrain worlds (never tethered)
-#endif
-#if NMF_HAS_TOPO(4)
-template __global__ void nmf_step_kernel<FlyTopoBio, false>(const DevModel*, DevState, ReplayArgs, int);
-template __global__ void nmf_step_kernel<FlyTopoBio, true>(const DevModel*, DevState, ReplayArgs, int);
-template __global__ void nmf_step_kernel<Terrain<FlyTopoBio>, false>(const DevModel*, DevState, ReplayArgs, int);     // terrain worlds (never tethered)
-#endif
-#if NMF_HAS_TOPO(5)
-template __global__ void nmf_step_kernel<FlyTopoAll, false>(const DevModel*, DevState, ReplayArgs, int);
-template __global__ void nmf_step_kernel<FlyTopoAll, true>(const DevModel*, DevState, ReplayArgs, int);
-template __global__ void nmf_step_kernel<Terrain<FlyTopoAll>, false>(const DevModel*, DevState, ReplayArgs, int);     // terrain worlds (never tethered)
-#endif
+// One kernel per family of NMF_FAMILIES (nmf_families.h) and world kind: plain, tethered (weld), terrain (never tethered)
+#define NMF_INSTANTIATE(k, TP, ...) NMF_IF_TOPO_##k(                                                      \
+  template __global__ void nmf_step_kernel<TP, false>(const DevModel*, DevState, ReplayArgs, int);        \
+  template __global__ void nmf_step_kernel<TP, true>(const DevModel*, DevState, ReplayArgs, int);         \
+  template __global__ void nmf_step_kernel<Terrain<TP>, false>(const DevModel*, DevState, ReplayArgs, int);)
+NMF_FAMILIES(NMF_INSTANTIATE)
+#undef NMF_INSTANTIATE
 
 }  // namespace nmf

@@ -1,5 +1,5 @@
 // nmf_step_lds.h — what a fly keeps in LDS while it steps, and the vocabulary every stage shares: the stage boundary (WSYNC),
-// the topology mask of development builds, the SolveReport bits, FlyLds / TreeLds with all their overlays (body poses on the
+// the SolveReport bits, FlyLds / TreeLds with all their overlays (body poses on the
 // solver vectors and the contact wrenches, AbaHandoff and the contact-space solve's Gram matrix on Ib..W, DualFactors on c_w +
 // c_m3), the kDual* layout constants, the model's hot part (HotModel), the contact info word, contact frames and the (leg,
 // component) lane roles.
@@ -16,13 +16,6 @@ namespace nmf {
 // wavefront-scope fence.  __syncthreads() (the round-1/2 behaviour) additionally parks the wave on `s_waitcnt lgkmcnt(0)`
 // until its LDS writes have drained: ~60 times per step, 1.2 % of the launch.
 #define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
-// NMF_TOPO_MASK (development builds only: `scripts/build_variant.sh x -DNMF_TOPO_MASK=1` compiles the LEGS_ONLY kernels alone,
-// in a sixth of the time): bit k keeps the kernels of topology k (0 LEGS_ONLY, 1 LEGS_ACTIVE_ONLY, 2 / 3 general tree,
-// 4 ALL_BIOLOGICAL, 5 ALL_POSSIBLE).  The shipped library has all of them.
-#ifndef NMF_TOPO_MASK
-#define NMF_TOPO_MASK 0x3f
-#endif
-#define NMF_HAS_TOPO(k) ((NMF_TOPO_MASK >> (k)) & 1)
 constexpr float kNoiseFactor = 8.f;
 // SolveReport: how the constraint solve of a step ended — one bit per kind, counted per world in stats_sum columns 4..15 (bit k ->
 // column 4 + k; include/nmf.h) and, for the launch's last step, in stats column 4 (the bits) / 5 (pivots) / 6 (KKT residual).
