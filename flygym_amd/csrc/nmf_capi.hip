@@ -467,7 +467,12 @@ int alloc_state(nmf_batch* b) {
   st.stats_sum = reinterpret_cast<unsigned int*>(stats_sum);
   st.dual_scratch = nullptr;
   // kDualGlob (ALL_POSSIBLE): the contact-space solve's leg factors live in HBM, one block per workgroup of a launch (<= n_worlds)
-  with_topo(b->topo, [&](auto tag) { if (nmf::kDualGlob<typename decltype(tag)::type>) alloc_dev(b, n_worlds * nmf::kDualScratchFloats, &st.dual_scratch); });
+  // kEulerFused (leg-chain kernels): Euler's factors, written by the smooth solve of the same step, likewise
+  with_topo(b->topo, [&](auto tag) {
+    using TP = typename decltype(tag)::type;
+    if (nmf::kDualGlob<TP>) alloc_dev(b, n_worlds * nmf::kDualScratchFloats, &st.dual_scratch);
+    else if (nmf::kEulerFused<TP>) alloc_dev(b, n_worlds * (size_t)nmf::euler_scratch_floats<TP>(), &st.dual_scratch);
+  });
   st.noslip_buf = nullptr;
   // CPU flavour: scratch of the primal path's noslip pass (157 KB per world)
   if (b->dm.noslip_iter > 0) alloc_dev(b, n_worlds * nmf::kNoslipFloats, &st.noslip_buf);

@@ -155,6 +155,12 @@ __global__ void __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(wave
   if (chunked && lane == 0) t_first = atomicAdd(&st.csched->ticket, 1u);
   stage_launch_constants(s, m);
   if constexpr (kDualGlob<TP>) { if (lane == 0) s.dual_glob[0] = st.dual_scratch + (size_t)blockIdx.x * kDualScratchFloats; }
+  if constexpr (kEulerFused<TP>) {
+    if (lane == 0) {
+      const unsigned long long p = (unsigned long long)(st.dual_scratch + (size_t)blockIdx.x * euler_scratch_floats<TP>());
+      s.euler_fac[0] = (unsigned int)p; s.euler_fac[1] = (unsigned int)(p >> 32);
+    }
+  }
   unsigned int t_next = (unsigned int)__builtin_amdgcn_readfirstlane((int)t_first);
   STAGE_INIT();
   const int n_chunks = chunked ? st.n_chunks : 1;

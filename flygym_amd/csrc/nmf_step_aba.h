@@ -3,7 +3,8 @@
 // contact stiffness rows (KLane, add_contact_K_row), aba_step* and aba_solve.  aba_solve reads a right-hand side and writes a
 // solution by vector id (FlyLds::vec), leaves T = twists(x), borrows T..W for the leg -> root hand-off (AbaHandoff) and, for the
 // contact-space solve, parks its factors where the dual_* accessors of this file say (c_w + c_m3, vA..vD or the workgroup's
-// scratch in HBM).
+// scratch in HBM).  On the leg-chain kernels the smooth solve's sweep also builds the Euler step's factors, which
+// aba_solve_stored then solves on (kEulerFused).
 //
 // Not self-contained: one of the stage headers that nmf_step.hip includes in stage order to form the stepping kernel's
 // translation unit, and it relies on the ones before it.
@@ -376,9 +377,36 @@ template <class TP> __device__ __forceinline__ float* dual_acc(FlyLds<TP>& s) { 
   }
 }
 
+// Euler's factors (kEulerFused, nmf_step_lds.h): the workgroup's slot — rows of 8 floats, [hinge tip to base][leg], then the
+// root's six — with the base address in scalar registers; callers add a lane offset (one vector register) and the step's row
+// (in the instruction)
+typedef __attribute__((address_space(1))) float* euler_fac_ptr;
+template <class TP> __device__ __forceinline__ euler_fac_ptr euler_fac_base(FlyLds<TP>& s) {
+  if constexpr (kEulerFused<TP>) {
+    const unsigned int lo = (unsigned int)__builtin_amdgcn_readfirstlane((int)s.euler_fac[0]);
+    const unsigned int hi = (unsigned int)__builtin_amdgcn_readfirstlane((int)s.euler_fac[1]);
+    return (euler_fac_ptr)((unsigned long long)hi << 32 | lo);
+  } else return nullptr;
+}
+// one root axis of the factor half of the root's elimination, as aba_solve's root block performs it: U is column e of IA (unit
+// axes), D its own entry; hands back U / D and 1 / D
+template <int e>
+__device__ __forceinline__ void aba_root_factor(float (&IA)[6], float& kout, float& invDout) {
+  const float U = IA[e];
+  const float b0 = grp8_bcast<0>(U), b1 = grp8_bcast<1>(U), b2 = grp8_bcast<2>(U), b3 = grp8_bcast<3>(U),
+              b4 = grp8_bcast<4>(U), b5 = grp8_bcast<5>(U);
+  const float D = e == 0 ? b0 : e == 1 ? b1 : e == 2 ? b2 : e == 3 ? b3 : e == 4 ? b4 : b5;
+  const float invD = __builtin_amdgcn_rcpf(D);
+  const float k = U * invD;
+  { const float bb[6] = {b0, b1, b2, b3, b4, b5}; fma6(IA, -k, bb); }
+  kout = k; invDout = invD;
+}
+
 // WITHK_ (leg-chain kernels that have the contact-space solve): the contact stiffness rows are compiled into the solve at all
 // — only the primal Newton loop's instantiation has them, so the two solves of an ordinary step (smooth, Euler) run a function
 // two thirds the size: the step's hot path has to share a 64 KB instruction cache.  Elsewhere one instantiation serves all.
+// RESTRICTION (kEulerFused kernels): the WITHK_ = false instantiation is the SMOOTH SOLVE ONLY — it ignores hdamp and withF
+// (hdamp = 0, no wrenches) and overwrites the workgroup's Euler factors; the Euler step's solves are aba_solve_stored.
 template <class TP, bool WELD, bool WITHK_ = true>
 __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool withK, float hdamp,
                           const GModel& m, int lane, bool store = false, bool withF = false) {
@@ -389,6 +417,10 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
   // withF: the contact wrenches in c_w act on their bodies as external forces (the Euler step's solve after a contact-space
   // constraint solve: J^T f is never projected onto the dofs)
   withF = kDual<TP> && __builtin_amdgcn_readfirstlane((int)withF) != 0;
+  // kFuse: this instantiation is the smooth solve only (hdamp = 0, no wrenches; Euler's solves are aba_solve_stored) and carries
+  // Euler's articulated inertia IAe — the same rows, the diagonal dlt instead of arm — through the same sweep
+  constexpr bool kFuse = kEulerFused<TP> && !WITHK_;
+  if constexpr (kFuse) { withF = false; hdamp = 0.f; }
   const float* tau = s.vec(tau_id);
   float* x = s.vec(x_id);
   Frame fr{};
@@ -418,6 +450,9 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
   const int rS = kShadow0 && L.r >= 6 ? 6 : L.rr;
   const lds_cptr Sleg = lds_pinned(&s.S[j0][0]), Sown = lds_pinned(&s.S[j0][rS]);
   constexpr int SW = row_width_s<TP>();
+  // (rows 0..5 store their U / D, lanes 6, 7 of the group 1 / D: the contact-space factors' idiom below)
+  euler_fac_ptr fac = nullptr, fac_root = nullptr;
+  if constexpr (kFuse) { fac = euler_fac_base(s) + (L.lg * 8 + (L.r < 6 ? L.r : 6)); fac_root = euler_fac_base(s) + (TP::NLEG * TP::NDL * 8 + (L.r < 6 ? L.r : 6)); }
   KLane KL;                             // contact stiffness rows: per-row constants from the launch's table
   if (withK) {
     const float* q = s.k_tab[L.rr];
@@ -444,19 +479,21 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
   }
   SUB(18);
   float IA[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float IAe[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // (kFuse)
   float pA = 0.f;
   // ---- backward sweep along the leg.  What a hinge reads — its motion subspace, diagonal term and force, and at a body's last
   // hinge the body's inertia row — does not depend on the chain, but LDS takes a wave's operations in order and the sweep also
   // stores (the factors the contact-space solve keeps): a read issued where it is used waits for its own round trip, three
   // times per hinge.  So the reads run ONE HINGE AHEAD of the arithmetic (software pipeline, written out: the stores may alias
   // for all the compiler knows, it will not move a read across them).
-  float n_sj[6], n_sown = 0.f, n_delta = 0.f, n_tau = 0.f, n_row[6];
+  float n_sj[6], n_sown = 0.f, n_delta = 0.f, n_delta_e = 0.f, n_tau = 0.f, n_row[6];
   auto fetch_hinge = [&](auto DN) {
     constexpr int dn = decltype(DN)::value;
 #pragma unroll
     for (int i = 0; i < 6; i++) n_sj[i] = Sleg[dn * SW + i];
     n_sown = Sown[dn * SW];
     n_delta = dof_delta(s, m, j0 + dn, hdamp);
+    if constexpr (kFuse) n_delta_e = s.dlt[j0 + dn];
     n_tau = tau[j0 + dn];
     if constexpr (TP::is_last(dn) && kHasIsym<TP>) {
 #pragma unroll
@@ -469,7 +506,7 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
     float sj[6], row[6];
 #pragma unroll
     for (int i = 0; i < 6; i++) { sj[i] = n_sj[i]; row[i] = n_row[i]; }
-    const float sown = n_sown, delta = n_delta, tj = n_tau;
+    const float sown = n_sown, delta = n_delta, delta_e = n_delta_e, tj = n_tau;
     if constexpr (d > 0) fetch_hinge(std::integral_constant<int, (d > 0 ? d - 1 : 0)>{});
     if constexpr (TP::is_last(d)) {          // entering a new body (going towards the root)
       const int b = b0 + TP::lbody(d);
@@ -482,6 +519,7 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
         }
         if (withK) for (int c = cs[TP::lbody(d)]; c < cs[TP::lbody(d) + 1]; ++c) add_contact_K_row(row, s, c, KL, fr, L.rr, walls);
         add6(IA, row);
+        if constexpr (kFuse) add6(IAe, row);
       } else {
         add_inertia_row(IA, s, b, IM);
         if constexpr (kDual<TP>) {
@@ -497,6 +535,11 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
     if constexpr (kKeepS) Sreg[d] = sown;        // shadow rows: zero (kShadow0), else row 5's (same T word, same value)
     float Uraw, invDraw;
     aba_step_scaled<kShadow0>(IA, pA, sj, sr, L.mask, delta, tj, Ureg[d], ureg[d], Uraw, invDraw);
+    if constexpr (kFuse) {      // the factor half of the same step on IAe (no right-hand side: that half is dead code here)
+      float pe = 0.f, UDe, uDe, Ue, invDe;
+      aba_step_scaled<kShadow0>(IAe, pe, sj, sr, L.mask, delta_e, 0.f, UDe, uDe, Ue, invDe);
+      fac[(TP::NDL - 1 - d) * TP::NLEG * 8] = L.r < 6 ? Ue * invDe : invDe;
+    }
     if constexpr (kDual<TP>) {
       if (store) {      // rows 0..5: U / sqrt D; lanes 6, 7 of the group: 1 / sqrt D
         const float rs = __builtin_sqrtf(invDraw);
@@ -510,10 +553,16 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
   // elimination below wants.  (Until round 5 through LDS: 7 stores, then 42 reads per lane.)
   constexpr bool kLegSumValu = TP::NLEG <= 8;
   float legs_row[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, legs_pA = 0.f;
+  float legs_row_e[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  static_assert(!kFuse || kLegSumValu, "the fused factor sweep sums the legs on the VALU");
   if constexpr (kLegSumValu) {
     const float gm = L.grp < TP::NLEG ? 1.f : 0.f;
 #pragma unroll
     for (int i = 0; i < 6; i++) legs_row[i] = groups_sum(gm * IA[i]);
+    if constexpr (kFuse) {
+#pragma unroll
+      for (int i = 0; i < 6; i++) legs_row_e[i] = groups_sum(gm * IAe[i]);
+    }
     legs_pA = groups_sum(gm * pA);
   } else {
 #pragma unroll
@@ -543,6 +592,11 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
     pA = 0.f;
     if constexpr (kDual<TP>) {
       if (withF) for (int c = cs_root0; c < cs_root1; ++c) pA -= dual_wrench(s)[c][L.rr];
+    }
+    if constexpr (kFuse) {      // (the root has no diagonal term: the two chains differ by what the legs hand over)
+#pragma unroll
+      for (int i = 0; i < 6; i++) IAe[i] = row[i];
+      add6(IAe, legs_row_e);
     }
     if constexpr (kLegSumValu) { add6(row, legs_row); pA += legs_pA; }
     else {
@@ -598,6 +652,11 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
       { const float bb[6] = {b0, b1, b2, b3, b4, b5}; fma6(IA, -k, bb); }
       pA += k * u;
       Ur[e] = kShadow0 ? k : L.mask * k; ur[e] = u * invD;
+      if constexpr (kFuse) {
+        float ke, invDe;
+        aba_root_factor<e>(IAe, ke, invDe);
+        fac_root[i * 8] = L.r < 6 ? ke : invDe;
+      }
       if constexpr (kDual<TP>) {
         if (store) {
           const float rs = __builtin_sqrtf(invD);
@@ -642,6 +701,114 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
   }
   SUB(20);
   }
+}
+
+// The Euler step's solve of (M + h B) x = tau [+ the contact wrenches in c_w as body forces] on the factors the smooth solve of
+// the same step left in the workgroup's scratch (kEulerFused): the right-hand-side half of aba_solve's backward sweep — bias
+// wrench, s . pA, u, u / D; no inertia, no LDS round trip on the chain — the root's six steps likewise, and aba_solve's forward
+// sweep.  Leaves T = twists(x).  A function of its own, not a run-time branch of aba_solve: the step's hot path shares a 64 KB
+// instruction cache.
+template <class TP>
+__device__ __noinline__ void aba_solve_stored(FlyLds<TP>& s, int tau_id, int x_id, const GModel& m, int lane, bool withF) {
+  static_assert(kEulerFused<TP> && TP::NLEG <= 8 && TP::NDL <= 16, "leg-chain kernels");
+  withF = __builtin_amdgcn_readfirstlane((int)withF) != 0;
+  SUB_T0();
+  SUB(18);
+  // the factors first: their round trip to L2 runs under the right-hand side's reads (the compiler orders the 34 loads as it
+  // likes and waits for all of them once, before the first hinge)
+  const LaneRole L = lane_role<TP>(lane);
+  constexpr int NE = TP::NDL + 6;
+  float Fk[NE], Fd[NE];      // U / D of this lane's row, 1 / D
+  {
+    const euler_fac_ptr fk = euler_fac_base(s) + (L.lg * 8 + L.rr), fd = euler_fac_base(s) + (L.lg * 8 + 6);
+    const euler_fac_ptr rk = euler_fac_base(s) + (TP::NLEG * TP::NDL * 8 + L.rr), rd = euler_fac_base(s) + (TP::NLEG * TP::NDL * 8 + 6);
+#pragma unroll
+    for (int e = 0; e < TP::NDL; ++e) { Fk[e] = fk[e * TP::NLEG * 8]; Fd[e] = fd[e * TP::NLEG * 8]; }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) { Fk[TP::NDL + i] = rk[i * 8]; Fd[TP::NDL + i] = rd[i * 8]; }
+  }
+  const float* tau = s.vec(tau_id);
+  float* x = s.vec(x_id);
+  const int j0 = TP::LD0 + L.lg * TP::NDL, b0 = TP::LB0 + L.lg * TP::NBL;
+  constexpr bool kShadow0 = row_width_s<TP>() > 6 && row_width_tw<TP>() > 6;      // (see aba_solve)
+  const int rS = kShadow0 && L.r >= 6 ? 6 : L.rr;
+  const lds_cptr Sown = lds_pinned(&s.S[j0][rS]);
+  constexpr int SW = row_width_s<TP>();
+  int cs[TP::NBL + 1], cs_root0 = 0, cs_root1 = 0;                         // contact ranges of the leg's bodies / the root
+  static_for<TP::NBL + 1>([&](auto I) { constexpr int l = decltype(I)::value; cs[l] = withF ? s.body_cstart[b0 + l] : 0; });
+  if (withF) { cs_root0 = s.body_cstart[0]; cs_root1 = s.body_cstart[1]; }
+  float Ureg[TP::NDL], ureg[TP::NDL], sown[TP::NDL], tj[TP::NDL];      // U / D (this lane's row), u / D, own axis component, force
+#pragma unroll
+  for (int d = 0; d < TP::NDL; ++d) { sown[d] = Sown[d * SW]; tj[d] = tau[j0 + d]; }
+  float pA = 0.f;
+  static_for<TP::NDL>([&](auto DD) {
+    constexpr int d = TP::NDL - 1 - decltype(DD)::value;
+    if constexpr (TP::is_last(d)) {          // entering a new body (going towards the root)
+      if (withF) {
+#pragma clang loop unroll(disable) vectorize(disable)
+        for (int c = cs[TP::lbody(d)]; c < cs[TP::lbody(d) + 1]; ++c) pA -= dual_wrench(s)[c][L.rr];
+      }
+    }
+    const float sr = kShadow0 ? sown[d] : L.mask * sown[d];
+    const float k = Fk[TP::NDL - 1 - d], invD = Fd[TP::NDL - 1 - d];
+    const float sp = grp8_sum(sr * pA);
+    const float u = tj[d] - sp;
+    pA += k * u;
+    Ureg[d] = kShadow0 ? k : L.mask * k; ureg[d] = u * invD;
+  });
+  const float gm = L.grp < TP::NLEG ? 1.f : 0.f;
+  const float legs_pA = groups_sum(gm * pA);
+  // ---- root (see aba_solve): world axes, generalized forces in as R tau_rot
+  float Ur[6], ur[6], Rm[3][3];
+  {
+    pA = 0.f;
+    if (withF) for (int c = cs_root0; c < cs_root1; ++c) pA -= dual_wrench(s)[c][L.rr];
+    pA += legs_pA;
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+      for (int c = 0; c < 3; c++) Rm[c][k] = s.S[3 + k][c];
+    float tw[6];
+    const float t3 = tau[3], t4 = tau[4], t5 = tau[5];
+#pragma unroll
+    for (int c = 0; c < 3; c++) { tw[c] = Rm[c][0] * t3 + Rm[c][1] * t4 + Rm[c][2] * t5; tw[3 + c] = tau[c]; }
+    static_for<6>([&](auto DD) {
+      constexpr int i = decltype(DD)::value;
+      constexpr int e = i < 3 ? 2 - i : 8 - i;          // angular z, y, x, then linear z, y, x
+      const float k = Fk[TP::NDL + i], invD = Fd[TP::NDL + i];
+      const float sp = grp8_bcast<e>(pA);
+      const float u = tw[e] - sp;
+      pA += k * u;
+      Ur[e] = kShadow0 ? k : L.mask * k; ur[e] = u * invD;
+    });
+  }
+  // ---- forward sweep: root (linear x, y, z, then angular x, y, z), then down the leg
+  float a = 0.f;
+  {
+    float xw[6];
+    static_for<6>([&](auto DD) {
+      constexpr int i = decltype(DD)::value;
+      constexpr int e = i < 3 ? 3 + i : i - 3;
+      const float xe = ur[e] - grp8_sum(Ur[e] * a);
+      xw[e] = xe;
+      a = (kShadow0 ? L.r : L.rr) == e ? a + xe : a;
+    });
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      x[k] = xw[3 + k];
+      x[3 + k] = Rm[0][k] * xw[0] + Rm[1][k] * xw[1] + Rm[2][k] * xw[2];
+    }
+  }
+  s.T[0][rS] = a;
+  static_for<TP::NDL>([&](auto DD) {
+    constexpr int d = decltype(DD)::value;
+    const float xj = ureg[d] - grp8_sum(Ureg[d] * a);
+    x[j0 + d] = xj;
+    a += xj * sown[d];
+    if constexpr (TP::is_last(d)) s.T[b0 + TP::lbody(d)][rS] = a;
+  });
+  WSYNC();
+  SUB(19);      // (the stage profile's "(all ABA) legs + root" row covers this solve as it covers aba_solve)
 }
 
 }  // namespace nmf

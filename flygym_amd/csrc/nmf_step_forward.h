@@ -622,12 +622,14 @@ __device__ void physics_integrate(FlyLds<TP>& s, const GModel& m, int lane, bool
       }
       WSYNC();
     }
-    aba_solve<TP, WELD, !kDual<TP>>(s, V_QFRC_SMOOTH, V_B, false, h, m, lane, false, true);
+    if constexpr (kEulerFused<TP>) aba_solve_stored<TP>(s, V_QFRC_SMOOTH, V_B, m, lane, true);      // (the smooth solve left the factors)
+    else aba_solve<TP, WELD, !kDual<TP>>(s, V_QFRC_SMOOTH, V_B, false, h, m, lane, false, true);
   }
   else {
     for (int j = lane; j < s.nv(); j += kWave) s.vA[j] = s.qfrc_smooth[j] + s.vD[j];
     WSYNC();
-    aba_solve<TP, WELD, !kDual<TP>>(s, V_A, V_B, false, h, m, lane);
+    if constexpr (kEulerFused<TP>) aba_solve_stored<TP>(s, V_A, V_B, m, lane, false);
+    else aba_solve<TP, WELD, !kDual<TP>>(s, V_A, V_B, false, h, m, lane);
   }
   // Semi-implicit Euler in one pass: qvel += h a, then positions with the NEW velocities — a hinge's own (the same lane holds
   // it), the root's from lanes 0..5 through scalar registers (no second trip through LDS, no lane working alone while 63 wait:

@@ -131,6 +131,28 @@ template <class TP> inline constexpr bool kDualH = dual_hybrid<TP>();
 template <class TP> inline constexpr bool kDual = kDualS<TP> || kDualH<TP>;
 template <class TP> inline constexpr bool kDualGlob = kDualH<TP> && dual_global<TP>();
 constexpr int kDualScratchFloats = 8 * 6 * 24;      // per workgroup: the leg factors of the largest skeleton (six legs of 24 hinges)
+// Leg-chain kernels: the smooth solve's backward sweep carries the Euler step's articulated inertia (diagonal dlt instead of arm)
+// beside its own and parks that chain's factors in the workgroup's scratch in HBM (DevState::dual_scratch; these kernels have
+// no other use for it): per leg hinge (tip to base) and leg a row of 8 floats — U / D of the six rows, 1 / D, pad —, then one
+// such row per root axis (every group eliminates the root redundantly: one copy).  Euler's solve (aba_solve_stored,
+// nmf_step_aba.h) is the right-hand-side half of a sweep on them.  Written and read by the same wave within one step, but not
+// by the same lanes: 1 / D, stored by lanes 6 and 7 of a group, is read by all eight; a shadow lane reads its twin's word, which
+// holds bit for bit what it would have computed; the root's rows, stored by all eight groups (the same values), are read by
+// all.  No fence: a wave's vector memory operations reach its CU's L1 in program order, a store and a later load of one wave to
+// the same address are served in that order, and non-inlined calls lie between the two (each begins with s_waitcnt vmcnt(0)) —
+// what the contact-space factors of kDualGlob rely on as well.  The slot is as small as that (2.3 KB for
+// LEGS_ONLY): with a pair per lane and step (8.7 KB) the resident workgroups' slots and their private scratch overflowed an
+// XCD's L2 and two thirds of the stores went out to memory (DESIGN_APPENDIX.md section K).
+// -DNMF_EULER_REFACTOR: Euler's solve factorises for itself as before, no scratch.
+template <class TP> constexpr bool euler_fused() {
+#ifdef NMF_EULER_REFACTOR
+  return false;
+#else
+  return has_cm3<TP>();
+#endif
+}
+template <class TP> inline constexpr bool kEulerFused = euler_fused<TP>();
+template <class TP> constexpr int euler_scratch_floats() { if constexpr (has_cm3<TP>()) return 8 * (TP::NLEG * TP::NDL + 6); else return 0; }      // (the leg-chain kernels, whatever the build's switch)
 constexpr int dual_g_floats(int ncon) { return 9 * ncon * (ncon + 1) / 2; }      // one 3x3 block per unordered pair of contacts
 template <class TP> constexpr int dual_max_con() {
   if constexpr (kDualH<TP>) {      // the contacts whose blocks fit T..W
@@ -196,6 +218,11 @@ struct __align__(16) FlyLds : TreeLds<TP> {
   // spatial inertia about the root origin: m, h, I (inertia * twist products; ABA rows via InertiaRowMap).  Rows are 11
   // floats apart where LDS allows: lane = body loops then hit 32 different banks (stride 10: bodies b and b + 16 collide)
   float Isym[kHasIsym<TP> ? TP::NB : 1][kHasIsym<TP> ? 21 : 1];   // the same as a symmetric 6x6 (upper triangle): row fetches of the star ABA
+  // kEulerFused: address of this workgroup's scratch for Euler's factors in HBM, low and high word (set once per launch;
+  // euler_fac_base).  Here because Ib's alignment leaves eight bytes free behind Isym on both leg-chain skeletons: the kernels'
+  // LDS stays what it was.  Words, not a pointer: an empty array of pointers would still align what follows to eight bytes and
+  // move Ib in the hybrid and tree kernels, which do not have the member's contents.
+  unsigned int euler_fac[kEulerFused<TP> ? 2 : 0];
   // (Ib, T, W are contiguous and 16-byte aligned: the contact-space solve (nmf_dual.h) keeps the Gram matrix of the contact directions there)
   alignas(kDualS<TP> ? 16 : 4) float Ib[TP::NB][kHasCm3<TP> ? 11 : 10];
   static_assert(6 * TP::NV >= 9 * (TP::NB - 1), "rotation matrices do not fit the solver vectors");
