@@ -356,6 +356,45 @@ __device__ __forceinline__ float grp8_bcast(float v) {
   constexpr int pattern = 0x18 | (I << 5);
   return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), pattern));
 }
+// Rank-1 downdate of a 6 x 6 matrix whose row r sits in lane r of an 8-lane group (lanes 6, 7: shadow rows),
+//   IA[c] = fma(nk, U of lane c, IA[c]),  c = 0 .. 5,
+// on the matrix pipe: v_mfma_f32_4x4x1_16B_f32 computes sixteen independent 4 x 4 outer products, one per quad — register i of
+// lane j of a quad receives (A of the quad's lane i) x (B of lane j) + C, one rounding per entry like v_fma_f32
+// (scripts/micro/mfma_gram_probe.hip).  A group is two quads: with B = the lane's own nk, the columns 0..3 want A = U of the
+// group's first quad in both quads, the columns 4..7 U of its second quad.  Two ways to put them there, both checked bit for bit
+// against the swizzle + v_pk_fma_f32 form by scripts/micro/aba_rank1_probe.hip:
+//   grp8_lo / grp8_hi: one DPP move each (row_shr:4 into banks 1 and 3, row_shl:4 into banks 0 and 2 of every 16-lane row);
+//   the instruction's own A broadcast (CBSZ = 1: the blocks of a pair take one block's A; ABID = which) — no move at all.
+// The second accumulator's registers 2 and 3 receive the shadow columns 6 and 7: never read, and fed from nothing (whatever the
+// registers hold — possibly a NaN, which stays in them).
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float grp8_lo(float v) {      // lanes 4..7 of every group take lanes 0..3
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0x114, 0xf, 0xa, false));
+}
+__device__ __forceinline__ float grp8_hi(float v) {      // lanes 0..3 of every group take lanes 4..7
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0x104, 0xf, 0x5, false));
+}
+// lane I (0..7) of every group to the whole group on the vector pipe: the half's copy, then a broadcast inside the quads
+template <int I>
+__device__ __forceinline__ float grp8_bcast_dpp(float v) {
+  constexpr int q = I & 3;
+  const float h = I < 4 ? grp8_lo(v) : grp8_hi(v);
+  return NMF_DPP(h, q | q << 2 | q << 4 | q << 6);      // quad_perm [q, q, q, q]
+}
+template <bool DPP_COPIES = false>
+__device__ __forceinline__ void grp8_rank1_mfma(float (&IA)[6], float nk, float U) {
+  float pad0, pad1;
+  asm volatile("" : "=v"(pad0), "=v"(pad1));      // whatever the registers hold (volatile: one pair per downdate, not one kept for all)
+  f32x4 lo = {IA[0], IA[1], IA[2], IA[3]}, hi = {IA[4], IA[5], pad0, pad1};
+  if constexpr (DPP_COPIES) {
+    lo = __builtin_amdgcn_mfma_f32_4x4x1f32(grp8_lo(U), nk, lo, 0, 0, 0);
+    hi = __builtin_amdgcn_mfma_f32_4x4x1f32(grp8_hi(U), nk, hi, 0, 0, 0);
+  } else {
+    lo = __builtin_amdgcn_mfma_f32_4x4x1f32(U, nk, lo, 1, 0, 0);
+    hi = __builtin_amdgcn_mfma_f32_4x4x1f32(U, nk, hi, 1, 1, 0);
+  }
+  IA[0] = lo[0]; IA[1] = lo[1]; IA[2] = lo[2]; IA[3] = lo[3]; IA[4] = hi[0]; IA[5] = hi[1];
+}
 // wave-wide min / max on the VALU (same DPP ladder as wave_sum); `idn` is the identity fed to the
 // rows a row_bcast step does not write
 #define NMF_DPP_OLD(old, v, ctrl, rows) __builtin_amdgcn_update_dpp((old), (v), (ctrl), (rows), 0xf, false)

@@ -302,8 +302,8 @@ __device__ __forceinline__ void aba_step(float (&IA)[6], float& pA, const float*
 // the same for the leg chains of the star sweeps, whose back-substitution needs (u - U.a) / D only: hands back U / D and
 // u / D (one register per dof less to keep, one multiply per dof less in the forward sweep).  `sr` is the lane's own axis
 // component with the shadow rows already zero.  SHADOW0: the forward sweep keeps its accelerations zero in the shadow
-// rows, so U / D needs no mask either.
-template <bool SHADOW0>
+// rows, so U / D needs no mask either.  MFMA: the downdate on the matrix pipe (grp8_rank1_mfma, nmf_device.h; kAbaRank1Mfma).
+template <bool SHADOW0, bool MFMA = false>
 __device__ __forceinline__ void aba_step_scaled(float (&IA)[6], float& pA, const float* sj, float sr, float mask, float delta,
                                                 float tauj, float& UDout, float& uDout, float& Uraw, float& invDraw) {
   f2 a01 = mk2(IA[0], IA[1]), a23 = mk2(IA[2], IA[3]), a45 = mk2(IA[4], IA[5]);
@@ -316,11 +316,14 @@ __device__ __forceinline__ void aba_step_scaled(float (&IA)[6], float& pA, const
   const float invD = __builtin_amdgcn_rcpf(D);
   const float u = tauj - sp;
   const float k = U * invD;
-  const f2 nk = mk2(-k, -k);
-  a01 = __builtin_elementwise_fma(nk, mk2(grp8_bcast<0>(U), grp8_bcast<1>(U)), a01);
-  a23 = __builtin_elementwise_fma(nk, mk2(grp8_bcast<2>(U), grp8_bcast<3>(U)), a23);
-  a45 = __builtin_elementwise_fma(nk, mk2(grp8_bcast<4>(U), grp8_bcast<5>(U)), a45);
-  IA[0] = a01.x; IA[1] = a01.y; IA[2] = a23.x; IA[3] = a23.y; IA[4] = a45.x; IA[5] = a45.y;
+  if constexpr (MFMA) grp8_rank1_mfma(IA, -k, U);
+  else {
+    const f2 nk = mk2(-k, -k);
+    a01 = __builtin_elementwise_fma(nk, mk2(grp8_bcast<0>(U), grp8_bcast<1>(U)), a01);
+    a23 = __builtin_elementwise_fma(nk, mk2(grp8_bcast<2>(U), grp8_bcast<3>(U)), a23);
+    a45 = __builtin_elementwise_fma(nk, mk2(grp8_bcast<4>(U), grp8_bcast<5>(U)), a45);
+    IA[0] = a01.x; IA[1] = a01.y; IA[2] = a23.x; IA[3] = a23.y; IA[4] = a45.x; IA[5] = a45.y;
+  }
   pA += k * u;
   UDout = SHADOW0 ? k : mask * k; uDout = u * invD;
   Uraw = U; invDraw = invD;
@@ -389,10 +392,17 @@ template <class TP> __device__ __forceinline__ euler_fac_ptr euler_fac_base(FlyL
   } else return nullptr;
 }
 // one root axis of the factor half of the root's elimination, as aba_solve's root block performs it: U is column e of IA (unit
-// axes), D its own entry; hands back U / D and 1 / D
-template <int e>
+// axes), D its own entry; hands back U / D and 1 / D.  MFMA: the downdate on the matrix pipe, D's broadcast on the vector pipe.
+template <int e, bool MFMA = false>
 __device__ __forceinline__ void aba_root_factor(float (&IA)[6], float& kout, float& invDout) {
   const float U = IA[e];
+  if constexpr (MFMA) {
+    const float invD = __builtin_amdgcn_rcpf(grp8_bcast_dpp<e>(U));
+    const float k = U * invD;
+    grp8_rank1_mfma(IA, -k, U);
+    kout = k; invDout = invD;
+    return;
+  }
   const float b0 = grp8_bcast<0>(U), b1 = grp8_bcast<1>(U), b2 = grp8_bcast<2>(U), b3 = grp8_bcast<3>(U),
               b4 = grp8_bcast<4>(U), b5 = grp8_bcast<5>(U);
   const float D = e == 0 ? b0 : e == 1 ? b1 : e == 2 ? b2 : e == 3 ? b3 : e == 4 ? b4 : b5;
@@ -420,6 +430,7 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
   // kFuse: this instantiation is the smooth solve only (hdamp = 0, no wrenches; Euler's solves are aba_solve_stored) and carries
   // Euler's articulated inertia IAe — the same rows, the diagonal dlt instead of arm — through the same sweep
   constexpr bool kFuse = kEulerFused<TP> && !WITHK_;
+  constexpr bool kR1 = kFuse && kAbaRank1Mfma<TP>;      // both chains' downdates on the matrix pipe
   if constexpr (kFuse) { withF = false; hdamp = 0.f; }
   const float* tau = s.vec(tau_id);
   float* x = s.vec(x_id);
@@ -534,10 +545,10 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
     const float sr = kShadow0 ? sown : L.mask * sown;
     if constexpr (kKeepS) Sreg[d] = sown;        // shadow rows: zero (kShadow0), else row 5's (same T word, same value)
     float Uraw, invDraw;
-    aba_step_scaled<kShadow0>(IA, pA, sj, sr, L.mask, delta, tj, Ureg[d], ureg[d], Uraw, invDraw);
+    aba_step_scaled<kShadow0, kR1>(IA, pA, sj, sr, L.mask, delta, tj, Ureg[d], ureg[d], Uraw, invDraw);
     if constexpr (kFuse) {      // the factor half of the same step on IAe (no right-hand side: that half is dead code here)
       float pe = 0.f, UDe, uDe, Ue, invDe;
-      aba_step_scaled<kShadow0>(IAe, pe, sj, sr, L.mask, delta_e, 0.f, UDe, uDe, Ue, invDe);
+      aba_step_scaled<kShadow0, kR1>(IAe, pe, sj, sr, L.mask, delta_e, 0.f, UDe, uDe, Ue, invDe);
       fac[(TP::NDL - 1 - d) * TP::NLEG * 8] = L.r < 6 ? Ue * invDe : invDe;
     }
     if constexpr (kDual<TP>) {
@@ -642,19 +653,24 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
       constexpr int i = decltype(DD)::value;
       constexpr int e = i < 3 ? 2 - i : 8 - i;          // angular z, y, x, then linear z, y, x
       const float U = IA[e];
-      const float b0 = grp8_bcast<0>(U), b1 = grp8_bcast<1>(U), b2 = grp8_bcast<2>(U), b3 = grp8_bcast<3>(U),
-                  b4 = grp8_bcast<4>(U), b5 = grp8_bcast<5>(U);
-      const float D = e == 0 ? b0 : e == 1 ? b1 : e == 2 ? b2 : e == 3 ? b3 : e == 4 ? b4 : b5;
+      float D;
+      [[maybe_unused]] float b0, b1, b2, b3, b4, b5;
+      if constexpr (kR1) D = grp8_bcast_dpp<e>(U);
+      else {
+        b0 = grp8_bcast<0>(U), b1 = grp8_bcast<1>(U), b2 = grp8_bcast<2>(U), b3 = grp8_bcast<3>(U), b4 = grp8_bcast<4>(U), b5 = grp8_bcast<5>(U);
+        D = e == 0 ? b0 : e == 1 ? b1 : e == 2 ? b2 : e == 3 ? b3 : e == 4 ? b4 : b5;
+      }
       const float sp = grp8_bcast<e>(pA);
       const float invD = __builtin_amdgcn_rcpf(D);
       const float u = tw[e] - sp;
       const float k = U * invD;
-      { const float bb[6] = {b0, b1, b2, b3, b4, b5}; fma6(IA, -k, bb); }
+      if constexpr (kR1) grp8_rank1_mfma(IA, -k, U);
+      else { const float bb[6] = {b0, b1, b2, b3, b4, b5}; fma6(IA, -k, bb); }
       pA += k * u;
       Ur[e] = kShadow0 ? k : L.mask * k; ur[e] = u * invD;
       if constexpr (kFuse) {
         float ke, invDe;
-        aba_root_factor<e>(IAe, ke, invDe);
+        aba_root_factor<e, kR1>(IAe, ke, invDe);
         fac_root[i * 8] = L.r < 6 ? ke : invDe;
       }
       if constexpr (kDual<TP>) {

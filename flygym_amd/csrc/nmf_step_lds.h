@@ -152,6 +152,17 @@ template <class TP> constexpr bool euler_fused() {
 #endif
 }
 template <class TP> inline constexpr bool kEulerFused = euler_fused<TP>();
+// Leg-chain kernels: the rank-1 downdates of the fused smooth solve's two chains (legs and root) run on the matrix pipe
+// (grp8_rank1_mfma, nmf_device.h) instead of six group broadcasts through the LDS crossbar and three v_pk_fma_f32 each — the
+// same multiply-adds, the same bits.  -DNMF_ABA_RANK1_VALU: the broadcasts and packed multiply-adds everywhere, as before.
+template <class TP> constexpr bool aba_rank1_mfma() {
+#ifdef NMF_ABA_RANK1_VALU
+  return false;
+#else
+  return euler_fused<TP>();
+#endif
+}
+template <class TP> inline constexpr bool kAbaRank1Mfma = aba_rank1_mfma<TP>();
 template <class TP> constexpr int euler_scratch_floats() { if constexpr (has_cm3<TP>()) return 8 * (TP::NLEG * TP::NDL + 6); else return 0; }      // (the leg-chain kernels, whatever the build's switch)
 constexpr int dual_g_floats(int ncon) { return 9 * ncon * (ncon + 1) / 2; }      // one 3x3 block per unordered pair of contacts
 template <class TP> constexpr int dual_max_con() {

@@ -1,14 +1,15 @@
 """Cycles per articulated-body sweep, in isolation (diagnostic).  usage: aba_microbench.py [--build] [--pair]
 
 --pair: the two solves of an ordinary step (smooth, then Euler's on the same configuration) timed together, both ways: Euler on
-the factors the smooth sweep stored (the shipped build) and Euler factorising for itself (-DNMF_EULER_REFACTOR)."""
+the factors the smooth sweep stored (the shipped build), the same with the sweep's rank-1 downdates on the vector pipe
+(-DNMF_ABA_RANK1_VALU), and Euler factorising for itself (-DNMF_EULER_REFACTOR)."""
 import ctypes, subprocess, sys
 from pathlib import Path
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 from flygym_amd import _native
 pair = "--pair" in sys.argv
-variants = {"stored": [], "refactor": ["-DNMF_EULER_REFACTOR"]} if pair else {"": []}
+variants = {"stored": [], "rank1_valu": ["-DNMF_ABA_RANK1_VALU"], "refactor": ["-DNMF_EULER_REFACTOR"]} if pair else {"": []}
 libs = {k: ROOT / "flygym_amd" / f"libnmf_hip_aba{'_' + k if k else ''}.so" for k in variants}
 if "--build" in sys.argv or not all(p.exists() for p in libs.values()):
     procs = [subprocess.Popen(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp",
