@@ -111,7 +111,6 @@ template <class TP> inline constexpr int kDualKeep = 0;
 #else
 template <class TP> inline constexpr int kDualKeep = kDualS<TP> ? 16 : 0;
 #endif
-constexpr int dual_root_axis(int i) { return i < 3 ? 2 - i : 8 - i; }     // elimination order of the root (aba_solve)
 
 // (dual_eliminate, the elimination itself: nmf_dual_chain.h — a header the host compiles too, scripts/micro/dual_resume_check.cpp)
 

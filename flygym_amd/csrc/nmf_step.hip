@@ -24,6 +24,7 @@
 #include "nmf_device.h"
 #include "nmf_step_lds.h"          // FlyLds and its overlays, layout constants, lane roles
 #include "nmf_step_diag.h"         // STAGE / SUB / TRACE macros (diagnostic builds)
+#include "nmf_tree_fwd.h"          // what the stage headers call of nmf_tree.h, declared
 #include "nmf_step_kinematics.h"   // stage_kinematics, stage_inertia
 #include "nmf_step_collision.h"    // terrain, stage_collision
 #include "nmf_step_aba.h"          // chain sweeps, aba_solve
@@ -83,7 +84,7 @@ __device__ __forceinline__ void stage_launch_constants(FlyLds<TP>& s, const GMod
 #pragma unroll
       for (int c = 0; c < 6; c++) {
         const int i = lane < c ? lane : c, jx = lane < c ? c : lane;
-        q[14 + c] = __int_as_float(i * 6 - i * (i - 1) / 2 + (jx - i));
+        q[14 + c] = __int_as_float(sym_idx(i, jx));
       }
     }
   }

@@ -1,6 +1,8 @@
 // nmf_step_aba.h — chain sweeps and articulated-body solves in the (leg, component) lane layout: for_dofs / for_bodies,
 // sweep_twists (x -> T), sweep_project (W -> S . W), mul_M, the inertia row maps (Ib rows through InertiaRowMap, Isym), the
-// contact stiffness rows (KLane, add_contact_K_row), aba_step* and aba_solve.  aba_solve reads a right-hand side and writes a
+// contact stiffness rows (KLane, add_contact_K_row), the solves' shared pieces — aba_step_core behind aba_step / aba_step_scaled,
+// aba_root_factor, ChainLane (lane set-up), FreeJointAxes, sub_contact_wrenches, aba_forward_sweep — and aba_solve /
+// aba_solve_stored, which are written with them.  aba_solve reads a right-hand side and writes a
 // solution by vector id (FlyLds::vec), leaves T = twists(x), borrows T..W for the leg -> root hand-off (AbaHandoff) and, for the
 // contact-space solve, parks its factors where the dual_* accessors of this file say (c_w + c_m3, vA..vD or the workgroup's
 // scratch in HBM).  On the leg-chain kernels the smooth solve's sweep also builds the Euler step's factors, which
@@ -12,25 +14,6 @@
 #include "nmf_device.h"
 
 namespace nmf {
-
-// sweeps of the rest of the body / of a general tree — declared here because nmf_tree.h, which defines them, has to come last in
-// the unit: its articulated-body passes are built from aba_step / add_contact_K_row of nmf_step_aba.h, whose aba_solve in turn
-// calls them
-template <class TP> __device__ void tree_sweep_twists(FlyLds<TP>& s, const float* x, float (*T)[row_width_tw<TP>()], const GModel& m, int lane);
-template <class TP, class Extra, class Emit>
-__device__ __forceinline__ void tree_sweep_project(FlyLds<TP>& s, float (*W)[row_width_tw<TP>()], const GModel& m, int lane, Extra&& extra, Emit&& emit);
-template <class TP, bool WELD>
-__device__ void tree_aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool withK, float hdamp, const GModel& m, int lane);
-template <class TP> __device__ void tree_sweep_twists_levels(FlyLds<TP>& s, const float* x, float (*T)[row_width_tw<TP>()], const GModel& m, int lane);
-template <class TP, class Extra>
-__device__ __forceinline__ void tree_gather_levels(FlyLds<TP>& s, float (*W)[row_width_tw<TP>()], const GModel& m, int lane, Extra&& extra);
-struct RestNode;
-template <class TP, bool FAST, bool UP, class F> __device__ __forceinline__ void rest_levels(FlyLds<TP>& s, int lane, F&& f);
-template <class TP, int NUM>
-__device__ __forceinline__ void rest_aba_eliminate(FlyLds<TP>& s, const RestNode& nd, const float* tau, bool withK, float hdamp,
-                                                   const Frame& fr, const LaneRole& L, const int (&so)[6], const struct InertiaRowMap& IM, const GModel& m);
-template <class TP, int NUM, bool HOMOGENEOUS>
-__device__ __forceinline__ void rest_aba_expand(FlyLds<TP>& s, const RestNode& nd, float* x, const LaneRole& L);
 
 // ------------------------------------------------------------------ chain sweeps
 // Lane layout for everything that walks a leg: the wave is 8 groups of 8 lanes; group g < NLEG owns
@@ -72,10 +55,7 @@ __device__ __forceinline__ SV rest_inertia_mul(const FlyLds<TP>& s, SV t) {
   for (int r = 0; r < 6; r++) {
     float acc = 0.f;
 #pragma unroll
-    for (int c = 0; c < 6; c++) {
-      const int i = r < c ? r : c, jx = r < c ? c : r;
-      acc += s.restA[i * 6 - i * (i - 1) / 2 + (jx - i)] * tv[c];
-    }
+    for (int c = 0; c < 6; c++) acc += s.restA[sym_idx(r, c)] * tv[c];
     o[r] = acc;
   }
   return SV{v3(o[0], o[1], o[2]), v3(o[3], o[4], o[5])};
@@ -279,43 +259,25 @@ __device__ __forceinline__ void add_contact_K_row(float* row, const FlyLds<TP>& 
 //                    IA -= U UT / D, pA += U (tau - s.pA) / D   (group sums by DPP)
 //   root           : IA_root a = (wrench of tau_root) - pA_root, 6x6 Cholesky in one lane
 //   forward sweep  : x_j = (u_j - U_j . a) / D_j,  a += s_j x_j
-// one articulated-body elimination step for hinge/axis `sj` (6 floats, group-uniform) with this lane's row IA,
-// bias component pA, own component `sown`, diagonal term delta and generalized force tauj
-__device__ __forceinline__ void aba_step(float (&IA)[6], float& pA, const float* sj, float sown, float mask, float delta,
-                                         float tauj, float& Uout, float& uout, float& invDout) {
-  // row arithmetic in packed float32, as in aba_step_scaled below
-  f2 acc = mk2(IA[0], IA[1]) * mk2(sj[0], sj[1]);
-  acc = __builtin_elementwise_fma(mk2(IA[2], IA[3]), mk2(sj[2], sj[3]), acc);
-  acc = __builtin_elementwise_fma(mk2(IA[4], IA[5]), mk2(sj[4], sj[5]), acc);
-  const float U = acc.x + acc.y;
-  const float sr = mask * sown;
-  const float D = grp8_sum(sr * U) + delta;
-  const float sp = grp8_sum(sr * pA);
-  const float invD = __builtin_amdgcn_rcpf(D);
-  const float u = tauj - sp;
-  const float k = U * invD;
-  { const float bb[6] = {grp8_bcast<0>(U), grp8_bcast<1>(U), grp8_bcast<2>(U), grp8_bcast<3>(U), grp8_bcast<4>(U), grp8_bcast<5>(U)};
-    fma6(IA, -k, bb); }
-  pA += k * u;
-  Uout = mask * U; uout = u; invDout = invD;
-}
-// the same for the leg chains of the star sweeps, whose back-substitution needs (u - U.a) / D only: hands back U / D and
-// u / D (one register per dof less to keep, one multiply per dof less in the forward sweep).  `sr` is the lane's own axis
-// component with the shadow rows already zero.  SHADOW0: the forward sweep keeps its accelerations zero in the shadow
-// rows, so U / D needs no mask either.  MFMA: the downdate on the matrix pipe (grp8_rank1_mfma, nmf_device.h; kAbaRank1Mfma).
-template <bool SHADOW0, bool MFMA = false>
-__device__ __forceinline__ void aba_step_scaled(float (&IA)[6], float& pA, const float* sj, float sr, float mask, float delta,
-                                                float tauj, float& UDout, float& uDout, float& Uraw, float& invDraw) {
+// one articulated-body elimination step for hinge/axis `sj` (6 floats, group-uniform) with this lane's row IA, bias component
+// pA, own axis component `sown`, diagonal term delta and generalized force tauj: the arithmetic (row products in packed float32)
+// and the downdate; aba_step / aba_step_scaled below differ in what they hand back only.  MASKED: `sown` still carries the
+// shadow rows' copy of row 5 and is masked here (after U, where aba_step always took the product: the order is in the code).
+// MFMA: the downdate on the matrix pipe (grp8_rank1_mfma, nmf_device.h; kAbaRank1Mfma).
+template <bool MFMA, bool MASKED>
+__device__ __forceinline__ void aba_step_core(float (&IA)[6], float& pA, const float* sj, float sown, float mask, float delta, float tauj,
+                                              float& U, float& u, float& invD, float& k) {
   f2 a01 = mk2(IA[0], IA[1]), a23 = mk2(IA[2], IA[3]), a45 = mk2(IA[4], IA[5]);
   f2 acc = a01 * mk2(sj[0], sj[1]);
   acc = __builtin_elementwise_fma(a23, mk2(sj[2], sj[3]), acc);
   acc = __builtin_elementwise_fma(a45, mk2(sj[4], sj[5]), acc);
-  const float U = acc.x + acc.y;
+  U = acc.x + acc.y;
+  const float sr = MASKED ? mask * sown : sown;
   const float D = grp8_sum(sr * U) + delta;
   const float sp = grp8_sum(sr * pA);
-  const float invD = __builtin_amdgcn_rcpf(D);
-  const float u = tauj - sp;
-  const float k = U * invD;
+  invD = __builtin_amdgcn_rcpf(D);
+  u = tauj - sp;
+  k = U * invD;
   if constexpr (MFMA) grp8_rank1_mfma(IA, -k, U);
   else {
     const f2 nk = mk2(-k, -k);
@@ -325,8 +287,23 @@ __device__ __forceinline__ void aba_step_scaled(float (&IA)[6], float& pA, const
     IA[0] = a01.x; IA[1] = a01.y; IA[2] = a23.x; IA[3] = a23.y; IA[4] = a45.x; IA[5] = a45.y;
   }
   pA += k * u;
-  UDout = SHADOW0 ? k : mask * k; uDout = u * invD;
-  Uraw = U; invDraw = invD;
+}
+// the rest-of-body passes (nmf_tree.h): own component `sown` unmasked; hands back U (shadow rows zero), u and 1 / D
+__device__ __forceinline__ void aba_step(float (&IA)[6], float& pA, const float* sj, float sown, float mask, float delta,
+                                         float tauj, float& Uout, float& uout, float& invDout) {
+  float U, k;
+  aba_step_core<false, true>(IA, pA, sj, sown, mask, delta, tauj, U, uout, invDout, k);
+  Uout = mask * U;
+}
+// the leg chains of the star sweeps, whose back-substitution needs (u - U.a) / D only: hands back U / D and u / D (one register
+// per dof less to keep, one multiply per dof less in the forward sweep).  SHADOW0: the forward sweep keeps its accelerations
+// zero in the shadow rows, so U / D needs no mask either.
+template <bool SHADOW0, bool MFMA = false>
+__device__ __forceinline__ void aba_step_scaled(float (&IA)[6], float& pA, const float* sj, float sr, float mask, float delta,
+                                                float tauj, float& UDout, float& uDout, float& Uraw, float& invDraw) {
+  float u, k;
+  aba_step_core<MFMA, false>(IA, pA, sj, sr, mask, delta, tauj, Uraw, u, invDraw, k);
+  UDout = SHADOW0 ? k : mask * k; uDout = u * invDraw;
 }
 // LDS pointer whose value the optimizer may not look through: the accesses made from it carry their (small, constant)
 // offsets in the instruction — a ds_read2 reaches 255 dwords — instead of one address add per access pair, which is what
@@ -391,11 +368,15 @@ template <class TP> __device__ __forceinline__ euler_fac_ptr euler_fac_base(FlyL
     return (euler_fac_ptr)((unsigned long long)hi << 32 | lo);
   } else return nullptr;
 }
-// one root axis of the factor half of the root's elimination, as aba_solve's root block performs it: U is column e of IA (unit
-// axes), D its own entry; hands back U / D and 1 / D.  MFMA: the downdate on the matrix pipe, D's broadcast on the vector pipe.
+// The root's six axes in elimination order: angular z, y, x, then linear z, y, x (both solves; the contact-space solve's root
+// factors, nmf_dual.h, are stored in it)
+constexpr int dual_root_axis(int i) { return i < 3 ? 2 - i : 8 - i; }
+// one root axis of the factor half of the root's elimination (both chains of aba_solve's root block): U is column e of IA (unit
+// axes), D its own entry; hands back U, U / D and 1 / D.  MFMA: the downdate on the matrix pipe, D's broadcast on the vector pipe.
 template <int e, bool MFMA = false>
-__device__ __forceinline__ void aba_root_factor(float (&IA)[6], float& kout, float& invDout) {
+__device__ __forceinline__ void aba_root_factor(float (&IA)[6], float& Uout, float& kout, float& invDout) {
   const float U = IA[e];
+  Uout = U;
   if constexpr (MFMA) {
     const float invD = __builtin_amdgcn_rcpf(grp8_bcast_dpp<e>(U));
     const float k = U * invD;
@@ -410,6 +391,98 @@ __device__ __forceinline__ void aba_root_factor(float (&IA)[6], float& kout, flo
   const float k = U * invD;
   { const float bb[6] = {b0, b1, b2, b3, b4, b5}; fma6(IA, -k, bb); }
   kout = k; invDout = invD;
+}
+
+// pA -= component rr of the contact wrenches c0 .. c1 - 1 (dual_wrench), as a body force.  ROLLED: the loop as it stands (in the
+// chain's backward sweep, where it sits once per body); the root's, once per solve, is left to the optimizer
+template <bool ROLLED, class TP>
+__device__ __forceinline__ void sub_contact_wrenches(float& pA, FlyLds<TP>& s, int c0, int c1, int rr) {
+  if constexpr (ROLLED) {
+#pragma clang loop unroll(disable) vectorize(disable)
+    for (int c = c0; c < c1; ++c) pA -= dual_wrench(s)[c][rr];
+  } else {
+    for (int c = c0; c < c1; ++c) pA -= dual_wrench(s)[c][rr];
+  }
+}
+
+
+// What a lane of either solve knows about its leg chain.  Shadow rows (r = 6, 7): where S and T have a padding column (S's is
+// zeroed at launch) they read their axis component from it and keep the acceleration sweep's value there: zero contributions to
+// every group sum without a mask multiply per dof (kShadow0).  Without padding they shadow row 5 and the sums are masked.
+// (L is the solve's own lane role, by reference: the column select below is then compiled where the solve is, as it was.)
+template <class TP>
+struct ChainLane {
+  static constexpr bool kShadow0 = row_width_s<TP>() > 6 && row_width_tw<TP>() > 6;
+  static constexpr int SW = row_width_s<TP>();
+  const LaneRole& L;
+  int j0, b0;                 // the leg's first dof / body
+  int rS;                     // the lane's column of S and T
+  lds_cptr Sleg, Sown;        // the leg's first axis / the lane's own component of it (rows SW apart)
+  __device__ __forceinline__ ChainLane(FlyLds<TP>& s, const LaneRole& L_) : L(L_) {
+    j0 = TP::LD0 + L.lg * TP::NDL; b0 = TP::LB0 + L.lg * TP::NBL;
+    rS = kShadow0 && L.r >= 6 ? 6 : L.rr;
+    Sleg = lds_pinned(&s.S[j0][0]); Sown = lds_pinned(&s.S[j0][rS]);
+  }
+  // the contact ranges of the leg's bodies (cs) and of the root; `any`: some contact term is in the solve (wave-uniform), else empty
+  __device__ __forceinline__ void contact_ranges(const FlyLds<TP>& s, bool any, int (&cs)[TP::NBL + 1], int& cs_root0, int& cs_root1) const {
+    static_for<TP::NBL + 1>([&](auto I) { constexpr int l = decltype(I)::value; cs[l] = any ? s.body_cstart[b0 + l] : 0; });
+    if (any) { cs_root0 = s.body_cstart[0]; cs_root1 = s.body_cstart[1]; }
+  }
+};
+
+// The free joint's rotation axes.  The root is eliminated in world axes (see aba_solve's root block): generalized forces go in
+// as R tau_rot, the rotational accelerations come out as RT alpha.
+struct FreeJointAxes {
+  float Rm[3][3];                       // Rm[c][k] = component c of the k-th rotation axis of the free joint
+  // reads the axes; tw = the wrench of tau[0..5] in world axes (angular, linear)
+  template <class TP> __device__ __forceinline__ void load(const FlyLds<TP>& s, const float* tau, float (&tw)[6]) {
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+      for (int c = 0; c < 3; c++) Rm[c][k] = s.S[3 + k][c];
+    const float t3 = tau[3], t4 = tau[4], t5 = tau[5];
+#pragma unroll
+    for (int c = 0; c < 3; c++) { tw[c] = Rm[c][0] * t3 + Rm[c][1] * t4 + Rm[c][2] * t5; tw[3 + c] = tau[c]; }
+  }
+  // the world-axis accelerations xw (angular, linear) as x[0..5]
+  __device__ __forceinline__ void accelerations(const float (&xw)[6], float* x) const {
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      x[k] = xw[3 + k];
+      x[3 + k] = Rm[0][k] * xw[0] + Rm[1][k] * xw[1] + Rm[2][k] * xw[2];
+    }
+  }
+};
+
+// The forward sweep of both solves: x_j = u_j / D_j - (U_j / D_j) . a,  a += s_j x_j — the root in world axes (linear x, y, z,
+// then angular x, y, z: the reverse of dual_root_axis) from Ur / ur, then down the leg from Ureg / ureg; own(d) is the lane's
+// own component of the leg's d-th axis.  Writes x, leaves T = twists(x).
+template <class TP, class Own>
+__device__ __forceinline__ void aba_forward_sweep(FlyLds<TP>& s, float* x, const ChainLane<TP>& C, const FreeJointAxes& R,
+                                                  const float (&Ur)[6], const float (&ur)[6], const float (&Ureg)[TP::NDL],
+                                                  const float (&ureg)[TP::NDL], Own&& own) {
+  const LaneRole& L = C.L;
+  float a = 0.f;
+  {
+    float xw[6];
+    static_for<6>([&](auto DD) {
+      constexpr int i = decltype(DD)::value;
+      constexpr int e = i < 3 ? 3 + i : i - 3;
+      const float xe = ur[e] - grp8_sum(Ur[e] * a);
+      xw[e] = xe;
+      a = (C.kShadow0 ? L.r : L.rr) == e ? a + xe : a;
+    });
+    R.accelerations(xw, x);
+  }
+  s.T[0][C.rS] = a;
+  static_for<TP::NDL>([&](auto DD) {
+    constexpr int d = decltype(DD)::value;
+    const float xj = ureg[d] - grp8_sum(Ureg[d] * a);
+    x[C.j0 + d] = xj;
+    a += xj * own(d);
+    if constexpr (TP::is_last(d)) s.T[C.b0 + TP::lbody(d)][C.rS] = a;
+  });
+  WSYNC();
 }
 
 // WITHK_ (leg-chain kernels that have the contact-space solve): the contact stiffness rows are compiled into the solve at all
@@ -438,7 +511,8 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
   if (withK) fr = ld_frame(s, m);
   const bool walls = TP::kTerrain && withK && __builtin_amdgcn_readfirstlane(s.nwall) != 0;      // terrain side faces in contact this step
   const LaneRole L = lane_role<TP>(lane);
-  const int j0 = TP::LD0 + L.lg * TP::NDL, b0 = TP::LB0 + L.lg * TP::NBL;
+  ChainLane<TP> C(s, L);
+  const int j0 = C.j0, b0 = C.b0;
   static_assert(sizeof(AbaHandoff<TP>) <= sizeof(float) * TP::NB * 12, "ABA hand-off does not fit T..W");
   AbaHandoff<TP>& H = *reinterpret_cast<AbaHandoff<TP>*>(&s.T[0][0]);
   // offsets of row rr inside a symmetric 6x6's packed storage (lane constants; the hybrid kernels' hand-off slots)
@@ -446,7 +520,7 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
 #pragma unroll
   for (int c = 0; c < 6; c++) {
     if constexpr (kHasIsym<TP>) so[c] = __float_as_int(s.k_tab[L.rr][14 + c]);
-    else { const int i = L.rr < c ? L.rr : c, jx = L.rr < c ? c : L.rr; so[c] = i * 6 - i * (i - 1) / 2 + (jx - i); }
+    else { const int i = L.rr < c ? L.rr : c, jx = L.rr < c ? c : L.rr; so[c] = sym_idx(i, jx); }
   }
   InertiaRowMap IM{};                                              // this lane's row of a body's 6x6 inertia, read out of Ib
   if constexpr (!kHasIsym<TP>) IM = inertia_map_unpack(s.k_tab[L.rr]);
@@ -454,13 +528,8 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
   // forward sweep instead of keeping it: 24 registers fewer to spill
   constexpr bool kKeepS = TP::NDL <= 16;
   float Ureg[TP::NDL], ureg[TP::NDL], Sreg[kKeepS ? TP::NDL : 1];        // U / D (this lane's row), u / D, own axis component
-  // Shadow rows (r = 6, 7).  Where S and T have a padding column (S's is zeroed at launch) they read their axis
-  // component from it and keep the acceleration sweep's value there: zero contributions to every group sum without a
-  // mask multiply per dof.  Without padding they shadow row 5 and the sums are masked.
-  constexpr bool kShadow0 = row_width_s<TP>() > 6 && row_width_tw<TP>() > 6;
-  const int rS = kShadow0 && L.r >= 6 ? 6 : L.rr;
-  const lds_cptr Sleg = lds_pinned(&s.S[j0][0]), Sown = lds_pinned(&s.S[j0][rS]);
-  constexpr int SW = row_width_s<TP>();
+  constexpr bool kShadow0 = ChainLane<TP>::kShadow0;
+  constexpr int SW = ChainLane<TP>::SW;
   // (rows 0..5 store their U / D, lanes 6, 7 of the group 1 / D: the contact-space factors' idiom below)
   euler_fac_ptr fac = nullptr, fac_root = nullptr;
   if constexpr (kFuse) { fac = euler_fac_base(s) + (L.lg * 8 + (L.r < 6 ? L.r : 6)); fac_root = euler_fac_base(s) + (TP::NLEG * TP::NDL * 8 + (L.r < 6 ? L.r : 6)); }
@@ -472,8 +541,7 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
     KL.ia = __float_as_int(q[9]); KL.ib = __float_as_int(q[10]);
   }
   int cs[TP::NBL + 1], cs_root0 = 0, cs_root1 = 0;                         // contact ranges of the leg's bodies / the root
-  static_for<TP::NBL + 1>([&](auto I) { constexpr int l = decltype(I)::value; cs[l] = withK || withF ? s.body_cstart[b0 + l] : 0; });
-  if (withK || withF) { cs_root0 = s.body_cstart[0]; cs_root1 = s.body_cstart[1]; }
+  C.contact_ranges(s, withK || withF, cs, cs_root0, cs_root1);
   // hybrid: the rest of the body (head, abdomen, wings, ...) is eliminated level by level first; its children-of-root
   // hand their articulated inertias to the root below through s.slot
   const bool red = rest_reduced(s);
@@ -501,8 +569,8 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
   auto fetch_hinge = [&](auto DN) {
     constexpr int dn = decltype(DN)::value;
 #pragma unroll
-    for (int i = 0; i < 6; i++) n_sj[i] = Sleg[dn * SW + i];
-    n_sown = Sown[dn * SW];
+    for (int i = 0; i < 6; i++) n_sj[i] = C.Sleg[dn * SW + i];
+    n_sown = C.Sown[dn * SW];
     n_delta = dof_delta(s, m, j0 + dn, hdamp);
     if constexpr (kFuse) n_delta_e = s.dlt[j0 + dn];
     n_tau = tau[j0 + dn];
@@ -522,23 +590,13 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
     if constexpr (TP::is_last(d)) {          // entering a new body (going towards the root)
       const int b = b0 + TP::lbody(d);
       if constexpr (kHasIsym<TP>) {
-        if constexpr (kDual<TP>) {
-          if (withF) {
-#pragma clang loop unroll(disable) vectorize(disable)
-            for (int c = cs[TP::lbody(d)]; c < cs[TP::lbody(d) + 1]; ++c) pA -= dual_wrench(s)[c][L.rr];
-          }
-        }
+        if constexpr (kDual<TP>) { if (withF) sub_contact_wrenches<true>(pA, s, cs[TP::lbody(d)], cs[TP::lbody(d) + 1], L.rr); }
         if (withK) for (int c = cs[TP::lbody(d)]; c < cs[TP::lbody(d) + 1]; ++c) add_contact_K_row(row, s, c, KL, fr, L.rr, walls);
         add6(IA, row);
         if constexpr (kFuse) add6(IAe, row);
       } else {
         add_inertia_row(IA, s, b, IM);
-        if constexpr (kDual<TP>) {
-          if (withF) {
-#pragma clang loop unroll(disable) vectorize(disable)
-            for (int c = cs[TP::lbody(d)]; c < cs[TP::lbody(d) + 1]; ++c) pA -= dual_wrench(s)[c][L.rr];
-          }
-        }
+        if constexpr (kDual<TP>) { if (withF) sub_contact_wrenches<true>(pA, s, cs[TP::lbody(d)], cs[TP::lbody(d) + 1], L.rr); }
         if (withK) for (int c = cs[TP::lbody(d)]; c < cs[TP::lbody(d) + 1]; ++c) add_contact_K_row(IA, s, c, KL, fr, L.rr, walls);
       }
     }
@@ -588,7 +646,7 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
   // update needs anyway) — 11 instead of 28 vector instructions per dof.  Generalized forces go in as R tau_rot, the
   // rotational accelerations come out as RT alpha.
   float Ur[6], ur[6];                   // U / D, u / D of the six root directions
-  float Rm[3][3];                       // Rm[c][k] = component c of the k-th rotation axis of the free joint
+  FreeJointAxes R;
   {
     float row[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if constexpr (kHasIsym<TP>) {
@@ -601,9 +659,7 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
       if constexpr (WELD) static_for<6>([&](auto I) { constexpr int i = decltype(I)::value; row[i] += L.rr == i ? s.weldD[i] : 0.f; });
     }
     pA = 0.f;
-    if constexpr (kDual<TP>) {
-      if (withF) for (int c = cs_root0; c < cs_root1; ++c) pA -= dual_wrench(s)[c][L.rr];
-    }
+    if constexpr (kDual<TP>) { if (withF) sub_contact_wrenches<false>(pA, s, cs_root0, cs_root1, L.rr); }
     if constexpr (kFuse) {      // (the root has no diagonal term: the two chains differ by what the legs hand over)
 #pragma unroll
       for (int i = 0; i < 6; i++) IAe[i] = row[i];
@@ -641,36 +697,20 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
     }
 #pragma unroll
     for (int i = 0; i < 6; i++) IA[i] = row[i];
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-#pragma unroll
-      for (int c = 0; c < 3; c++) Rm[c][k] = s.S[3 + k][c];
     float tw[6];
-    const float t3 = tau[3], t4 = tau[4], t5 = tau[5];
-#pragma unroll
-    for (int c = 0; c < 3; c++) { tw[c] = Rm[c][0] * t3 + Rm[c][1] * t4 + Rm[c][2] * t5; tw[3 + c] = tau[c]; }
+    R.load(s, tau, tw);
     static_for<6>([&](auto DD) {
       constexpr int i = decltype(DD)::value;
-      constexpr int e = i < 3 ? 2 - i : 8 - i;          // angular z, y, x, then linear z, y, x
-      const float U = IA[e];
-      float D;
-      [[maybe_unused]] float b0, b1, b2, b3, b4, b5;
-      if constexpr (kR1) D = grp8_bcast_dpp<e>(U);
-      else {
-        b0 = grp8_bcast<0>(U), b1 = grp8_bcast<1>(U), b2 = grp8_bcast<2>(U), b3 = grp8_bcast<3>(U), b4 = grp8_bcast<4>(U), b5 = grp8_bcast<5>(U);
-        D = e == 0 ? b0 : e == 1 ? b1 : e == 2 ? b2 : e == 3 ? b3 : e == 4 ? b4 : b5;
-      }
-      const float sp = grp8_bcast<e>(pA);
-      const float invD = __builtin_amdgcn_rcpf(D);
+      constexpr int e = dual_root_axis(i);
+      float U, k, invD;
+      aba_root_factor<e, kR1>(IA, U, k, invD);
+      const float sp = grp8_bcast<e>(pA);      // (the right-hand-side half goes round the factor step)
       const float u = tw[e] - sp;
-      const float k = U * invD;
-      if constexpr (kR1) grp8_rank1_mfma(IA, -k, U);
-      else { const float bb[6] = {b0, b1, b2, b3, b4, b5}; fma6(IA, -k, bb); }
       pA += k * u;
       Ur[e] = kShadow0 ? k : L.mask * k; ur[e] = u * invD;
       if constexpr (kFuse) {
-        float ke, invDe;
-        aba_root_factor<e, kR1>(IAe, ke, invDe);
+        float Ue, ke, invDe;
+        aba_root_factor<e, kR1>(IAe, Ue, ke, invDe);
         fac_root[i * 8] = L.r < 6 ? ke : invDe;
       }
       if constexpr (kDual<TP>) {
@@ -681,33 +721,7 @@ __device__ __noinline__ void aba_solve(FlyLds<TP>& s, int tau_id, int x_id, bool
       }
     });
   }
-  // ---- forward sweep: root (linear x, y, z, then angular x, y, z), then down the leg
-  float a = 0.f;
-  {
-    float xw[6];
-    static_for<6>([&](auto DD) {
-      constexpr int i = decltype(DD)::value;
-      constexpr int e = i < 3 ? 3 + i : i - 3;
-      const float xe = ur[e] - grp8_sum(Ur[e] * a);
-      xw[e] = xe;
-      a = (kShadow0 ? L.r : L.rr) == e ? a + xe : a;
-    });
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      x[k] = xw[3 + k];
-      x[3 + k] = Rm[0][k] * xw[0] + Rm[1][k] * xw[1] + Rm[2][k] * xw[2];
-    }
-  }
-  s.T[0][rS] = a;
-  static_for<TP::NDL>([&](auto DD) {
-    constexpr int d = decltype(DD)::value;
-    const int j = j0 + d;
-    const float xj = ureg[d] - grp8_sum(Ureg[d] * a);
-    x[j] = xj;
-    if constexpr (kKeepS) a += xj * Sreg[d]; else a += xj * Sown[d * SW];
-    if constexpr (TP::is_last(d)) s.T[b0 + TP::lbody(d)][rS] = a;
-  });
-  WSYNC();
+  aba_forward_sweep(s, x, C, R, Ur, ur, Ureg, ureg, [&](int d) { if constexpr (kKeepS) return Sreg[d]; else return C.Sown[d * SW]; });
   SUB(19);
   if constexpr (TP::REST_B > 0) {
     if (!red) {
@@ -733,6 +747,7 @@ __device__ __noinline__ void aba_solve_stored(FlyLds<TP>& s, int tau_id, int x_i
   // the factors first: their round trip to L2 runs under the right-hand side's reads (the compiler orders the 34 loads as it
   // likes and waits for all of them once, before the first hinge)
   const LaneRole L = lane_role<TP>(lane);
+  ChainLane<TP> C(s, L);
   constexpr int NE = TP::NDL + 6;
   float Fk[NE], Fd[NE];      // U / D of this lane's row, 1 / D
   {
@@ -745,25 +760,17 @@ __device__ __noinline__ void aba_solve_stored(FlyLds<TP>& s, int tau_id, int x_i
   }
   const float* tau = s.vec(tau_id);
   float* x = s.vec(x_id);
-  const int j0 = TP::LD0 + L.lg * TP::NDL, b0 = TP::LB0 + L.lg * TP::NBL;
-  constexpr bool kShadow0 = row_width_s<TP>() > 6 && row_width_tw<TP>() > 6;      // (see aba_solve)
-  const int rS = kShadow0 && L.r >= 6 ? 6 : L.rr;
-  const lds_cptr Sown = lds_pinned(&s.S[j0][rS]);
-  constexpr int SW = row_width_s<TP>();
+  constexpr bool kShadow0 = ChainLane<TP>::kShadow0;
   int cs[TP::NBL + 1], cs_root0 = 0, cs_root1 = 0;                         // contact ranges of the leg's bodies / the root
-  static_for<TP::NBL + 1>([&](auto I) { constexpr int l = decltype(I)::value; cs[l] = withF ? s.body_cstart[b0 + l] : 0; });
-  if (withF) { cs_root0 = s.body_cstart[0]; cs_root1 = s.body_cstart[1]; }
+  C.contact_ranges(s, withF, cs, cs_root0, cs_root1);
   float Ureg[TP::NDL], ureg[TP::NDL], sown[TP::NDL], tj[TP::NDL];      // U / D (this lane's row), u / D, own axis component, force
 #pragma unroll
-  for (int d = 0; d < TP::NDL; ++d) { sown[d] = Sown[d * SW]; tj[d] = tau[j0 + d]; }
+  for (int d = 0; d < TP::NDL; ++d) { sown[d] = C.Sown[d * C.SW]; tj[d] = tau[C.j0 + d]; }
   float pA = 0.f;
   static_for<TP::NDL>([&](auto DD) {
     constexpr int d = TP::NDL - 1 - decltype(DD)::value;
     if constexpr (TP::is_last(d)) {          // entering a new body (going towards the root)
-      if (withF) {
-#pragma clang loop unroll(disable) vectorize(disable)
-        for (int c = cs[TP::lbody(d)]; c < cs[TP::lbody(d) + 1]; ++c) pA -= dual_wrench(s)[c][L.rr];
-      }
+      if (withF) sub_contact_wrenches<true>(pA, s, cs[TP::lbody(d)], cs[TP::lbody(d) + 1], L.rr);
     }
     const float sr = kShadow0 ? sown[d] : L.mask * sown[d];
     const float k = Fk[TP::NDL - 1 - d], invD = Fd[TP::NDL - 1 - d];
@@ -775,22 +782,17 @@ __device__ __noinline__ void aba_solve_stored(FlyLds<TP>& s, int tau_id, int x_i
   const float gm = L.grp < TP::NLEG ? 1.f : 0.f;
   const float legs_pA = groups_sum(gm * pA);
   // ---- root (see aba_solve): world axes, generalized forces in as R tau_rot
-  float Ur[6], ur[6], Rm[3][3];
+  float Ur[6], ur[6];
+  FreeJointAxes R;
   {
     pA = 0.f;
-    if (withF) for (int c = cs_root0; c < cs_root1; ++c) pA -= dual_wrench(s)[c][L.rr];
+    if (withF) sub_contact_wrenches<false>(pA, s, cs_root0, cs_root1, L.rr);
     pA += legs_pA;
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-#pragma unroll
-      for (int c = 0; c < 3; c++) Rm[c][k] = s.S[3 + k][c];
     float tw[6];
-    const float t3 = tau[3], t4 = tau[4], t5 = tau[5];
-#pragma unroll
-    for (int c = 0; c < 3; c++) { tw[c] = Rm[c][0] * t3 + Rm[c][1] * t4 + Rm[c][2] * t5; tw[3 + c] = tau[c]; }
+    R.load(s, tau, tw);
     static_for<6>([&](auto DD) {
       constexpr int i = decltype(DD)::value;
-      constexpr int e = i < 3 ? 2 - i : 8 - i;          // angular z, y, x, then linear z, y, x
+      constexpr int e = dual_root_axis(i);
       const float k = Fk[TP::NDL + i], invD = Fd[TP::NDL + i];
       const float sp = grp8_bcast<e>(pA);
       const float u = tw[e] - sp;
@@ -798,32 +800,7 @@ __device__ __noinline__ void aba_solve_stored(FlyLds<TP>& s, int tau_id, int x_i
       Ur[e] = kShadow0 ? k : L.mask * k; ur[e] = u * invD;
     });
   }
-  // ---- forward sweep: root (linear x, y, z, then angular x, y, z), then down the leg
-  float a = 0.f;
-  {
-    float xw[6];
-    static_for<6>([&](auto DD) {
-      constexpr int i = decltype(DD)::value;
-      constexpr int e = i < 3 ? 3 + i : i - 3;
-      const float xe = ur[e] - grp8_sum(Ur[e] * a);
-      xw[e] = xe;
-      a = (kShadow0 ? L.r : L.rr) == e ? a + xe : a;
-    });
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      x[k] = xw[3 + k];
-      x[3 + k] = Rm[0][k] * xw[0] + Rm[1][k] * xw[1] + Rm[2][k] * xw[2];
-    }
-  }
-  s.T[0][rS] = a;
-  static_for<TP::NDL>([&](auto DD) {
-    constexpr int d = decltype(DD)::value;
-    const float xj = ureg[d] - grp8_sum(Ureg[d] * a);
-    x[j0 + d] = xj;
-    a += xj * sown[d];
-    if constexpr (TP::is_last(d)) s.T[b0 + TP::lbody(d)][rS] = a;
-  });
-  WSYNC();
+  aba_forward_sweep(s, x, C, R, Ur, ur, Ureg, ureg, [&](int d) { return sown[d]; });
   SUB(19);      // (the stage profile's "(all ABA) legs + root" row covers this solve as it covers aba_solve)
 }
 

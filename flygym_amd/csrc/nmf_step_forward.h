@@ -11,11 +11,6 @@
 
 namespace nmf {
 
-// velocities and bias accelerations of a general tree — declared here because nmf_tree.h, which defines them, has to come last
-// in the unit: its articulated-body passes are built from aba_step / add_contact_K_row of nmf_step_aba.h, whose aba_solve in
-// turn calls them
-template <class TP> __device__ void tree_velocity_bias(FlyLds<TP>& s, const GModel& m, int lane);
-
 template <class TP, bool WELD>
 __device__ bool physics_forward(FlyLds<TP>& s, const GModel& m, int lane, const DevState& st, int w, bool last, float* rec, CtrlPrefetch& pf STAGE_ARG) {
   // hybrid kernels: per-lane addresses are rebuilt every step instead of living across the item loop — hoisted, they left

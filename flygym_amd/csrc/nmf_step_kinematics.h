@@ -10,11 +10,6 @@
 
 namespace nmf {
 
-// the rest-of-body / general-tree part of the chain of transforms — declared here because nmf_tree.h, which defines them, has to
-// come last in the unit: its articulated-body passes are built from aba_step / add_contact_K_row of nmf_step_aba.h, whose
-// aba_solve in turn calls them
-template <class TP> __device__ void tree_kinematics_chain(FlyLds<TP>& s, const GModel& m, int lane, float (*relm)[12]);
-
 // ------------------------------------------------------------------ kinematics
 template <class TP>
 __device__ __noinline__ void stage_kinematics(FlyLds<TP>& s, const GModel& m, int lane) {

@@ -10,6 +10,7 @@
 // resident state, same shared stages (collision, contact rows, Newton loop, sensors) as the star kernels; the oracle
 // (oracle/nmf_oracle.c) is the same for both.  Slower per fly (few lanes busy per pass) — this is the generality path.
 #pragma once
+#include "nmf_tree_fwd.h"      // (the default of rest_levels' lane mapping is there)
 
 namespace nmf {
 
@@ -42,20 +43,6 @@ __device__ __forceinline__ RestNode rest_unpack(unsigned int w0, unsigned int w1
   nd.cstart = w1 & 255; nd.k = (w1 >> 8) & 255;
   return nd;
 }
-template <class TP, bool UP, class F>
-__device__ __forceinline__ void rest_levels_lane(FlyLds<TP>& s, int lane, F&& f) {
-  const int nl = __builtin_amdgcn_readfirstlane((int)s.t_nlevel) - 1;      // levels below the root
-  unsigned int w0[kRestLevels], w1[kRestLevels];
-#pragma unroll
-  for (int l = 0; l < kRestLevels; ++l) { w0[l] = s.t_pack[l][lane & 7][0]; w1[l] = s.t_pack[l][lane & 7][1]; }
-  static_for<kRestLevels>([&](auto I) {
-    constexpr int l = UP ? kRestLevels - 1 - decltype(I)::value : decltype(I)::value;
-    if (l < nl) {
-      if (lane < 8 && w0[l] != 0xffffffffu) f(rest_unpack(w0[l], w1[l]));
-      WSYNC();
-    }
-  });
-}
 
 // rigid transforms down the tree: R_b = R_parent Rrel_b, p_b = p_parent + R_parent off_b  (relm[b] = Rrel (9), off (3))
 template <class TP>
@@ -73,7 +60,7 @@ __device__ void tree_kinematics_chain(FlyLds<TP>& s, const GModel& m, int lane, 
     for (int i = 0; i < 9; ++i) s.xmat()[b][i] = out[i];
   };
   if constexpr (TP::kStar) {
-    if (m.rest_fast) { rest_levels_lane<TP, false>(s, lane, [&](const RestNode& nd) { body(nd.b, nd.parent); }); return; }
+    if (m.rest_fast) { rest_levels<TP, true, false, true>(s, lane, [&](const RestNode& nd) { body(nd.b, nd.parent); }); return; }
   }
   tree_down(s, lane, [&](int b) { body(b, (int)s.t_parent[b]); });
 }
@@ -100,7 +87,7 @@ template <class TP>
 __device__ void tree_velocity_bias_levels(FlyLds<TP>& s, const GModel& m, int lane) {
   if constexpr (TP::kStar) {
     if (m.rest_fast) {
-      rest_levels_lane<TP, false>(s, lane, [&](const RestNode& nd) {
+      rest_levels<TP, true, false, true>(s, lane, [&](const RestNode& nd) {
         SV v = ldsv(s.W[nd.parent]), a = ldsv(s.T[nd.parent]);
         SV S[3]; float qd[3];
 #pragma unroll
@@ -283,18 +270,21 @@ __device__ __forceinline__ RestNode rest_node_tbl(const FlyLds<TP>& s, int k) {
   return nd;
 }
 
-// f(node) for every body of the rest, level by level: UP = deepest level first
-template <class TP, bool FAST, bool UP, class F>
+// f(node) for every body of the rest, level by level: UP = deepest level first.  The g-th body of a level is the 8-lane group
+// g's (the articulated-body passes) or, LANE_PER_BODY (FAST only), lane g's alone (kinematics, velocities).
+template <class TP, bool FAST, bool UP, bool LANE_PER_BODY, class F>
 __device__ __forceinline__ void rest_levels(FlyLds<TP>& s, int lane, F&& f) {
+  static_assert(FAST || !LANE_PER_BODY, "a lane per body: the packed tables only");
   const int nl = __builtin_amdgcn_readfirstlane((int)s.t_nlevel) - 1;      // levels below the root
   if constexpr (FAST) {
+    const int g = LANE_PER_BODY ? lane & 7 : lane >> 3;
     unsigned int w0[kRestLevels], w1[kRestLevels];
 #pragma unroll
-    for (int l = 0; l < kRestLevels; ++l) { w0[l] = s.t_pack[l][lane >> 3][0]; w1[l] = s.t_pack[l][lane >> 3][1]; }
+    for (int l = 0; l < kRestLevels; ++l) { w0[l] = s.t_pack[l][g][0]; w1[l] = s.t_pack[l][g][1]; }
     static_for<kRestLevels>([&](auto I) {
       constexpr int l = UP ? kRestLevels - 1 - decltype(I)::value : decltype(I)::value;
       if (l < nl) {
-        if (w0[l] != 0xffffffffu) f(rest_unpack(w0[l], w1[l]));
+        if ((!LANE_PER_BODY || lane < 8) && w0[l] != 0xffffffffu) f(rest_unpack(w0[l], w1[l]));
         WSYNC();
       }
     });
@@ -305,16 +295,6 @@ __device__ __forceinline__ void rest_levels(FlyLds<TP>& s, int lane, F&& f) {
       WSYNC();
     }
   }
-}
-
-// the dofs of a body, last to first (REV) or first to last; NUM > 0: a compile-time count (fully unrolled, so the LDS
-// loads of all dofs are issued up front), NUM == 0: the run-time count
-template <int NUM, bool REV, class F>
-__device__ __forceinline__ void rest_dofs(int adr, int num, F&& f) {
-  if constexpr (NUM > 0) {
-    static_for<NUM>([&](auto I) { constexpr int i = decltype(I)::value; f(adr + (REV ? NUM - 1 - i : i)); });
-  } else if (REV) { for (int j = adr + num - 1; j >= adr; --j) f(j); }
-  else { for (int j = adr; j < adr + num; ++j) f(j); }
 }
 
 // full elimination of a body: matrix factors and vector part
