@@ -163,6 +163,8 @@ def lib():
             "nmf_camera_plan_create": (vp, [vp, vp, ci, vp, ci, vp, vp, vp, ci]),
             "nmf_camera_plan_destroy": (None, [vp]),
             "nmf_camera_render": (ci, [vp, vp, vp, vp, vp]),
+            "nmf_camera_plan_create_flies": (vp, [vp, ci, vp, vp, ci, vp, ci]),
+            "nmf_camera_render_flies": (ci, [vp, vp, vp, vp]),
             "nmf_cpg_params_size": (ctypes.c_size_t, []),
             "nmf_cpg_create": (vp, [vp, vp, vp, vp, vp]),
             "nmf_cpg_destroy": (None, [vp]),

@@ -1002,15 +1002,21 @@ extern "C" int nmf_eye_render_planned(nmf_batch* b, const nmf_eye_params* p, con
 }
 
 // ---- batch camera renderer (nmf_camera.hip) ----
-// Everything a render needs besides the batch's poses and the caller's spheres: an explicit handle with its own device copies.
+// Everything a render needs besides the batches' poses and the caller's spheres: an explicit handle with its own device copies.
+// One plan type for both entries: nmf_camera_plan_create makes a plan of one fly that nmf_camera_render draws with
+// nmf_camera_kernel, nmf_camera_plan_create_flies one of `flies.n_flies` flies for nmf_camera_render_flies.
 struct nmf_camera_plan {
-  const nmf_batch* batch = nullptr;
-  int n_cameras = 0, n_selected = 0, n_caps = 0;
+  const nmf_batch* batch = nullptr;           // the first fly's batch: the plan's device, and the owner nmf_camera_render asks for
+  bool several = false;                       // made by nmf_camera_plan_create_flies
+  int n_cameras = 0, n_selected = 0;
   nmf::CamArgs args{};
-  bool spheres_per_world = false;
-  nmf::CamView* views = nullptr; int* world_ids = nullptr; int* cap_seg = nullptr; float* cap_geom = nullptr; unsigned int* cap_rgb = nullptr;
+  nmf::CamFlies flies{};                      // per fly: the batch's pose arrays, the plan's copies of the capsule arrays
+  nmf::CamView* views = nullptr; int* world_ids = nullptr;
   DevMem mem;
 };
+
+static_assert(NMF_CAMERA_MAX_FLIES == nmf::kCamMaxFlies && NMF_CAMERA_MAX == nmf::kCamMaxViews && NMF_CAMERA_MAX_CAPSULES == nmf::kCamMaxCaps,
+              "include/nmf.h and nmf_camera.hip disagree on the renderer's limits");
 
 extern "C" size_t nmf_camera_params_size(void) { return sizeof(nmf_camera_params); }
 
@@ -1020,42 +1026,49 @@ extern "C" void nmf_camera_plan_destroy(nmf_camera_plan* P) {
   delete P;
 }
 
-static int fill_camera_plan(nmf_camera_plan* P, const nmf_batch* b, const nmf_camera_params* p, int n_cameras, const int32_t* world_ids, int n_selected,
-                            const int32_t* cap_seg, const float* cap_geom, const uint8_t* cap_rgb, int n_caps) {
-  const nmf_model* m = b->model;
-  if (n_cameras < 1 || n_cameras > NMF_CAMERA_MAX) return fail("nmf_camera_plan_create: need 1 <= n_cameras <= 8");
-  if (p->height < 1 || p->width < 1 || (int64_t)p->height * p->width > (1 << 26)) return fail("nmf_camera_plan_create: height and width must be at least 1 (and height * width at most 2^26)");
-  if (!world_ids || n_selected < 1) return fail("nmf_camera_plan_create: at least one world must be selected");
+// `who`: the entry point, for the error texts.  cam_fly: null = every camera belongs to fly 0.
+static int fill_camera_plan(nmf_camera_plan* P, const std::string& who, const nmf_camera_fly* flies, int n_flies, const nmf_camera_params* p,
+                            const int32_t* cam_fly, int n_cameras, const int32_t* world_ids, int n_selected) {
+  const nmf_batch* b = flies[0].batch;
+  if (n_cameras < 1 || n_cameras > NMF_CAMERA_MAX) return fail(who + ": need 1 <= n_cameras <= 8");
+  if (p->height < 1 || p->width < 1 || (int64_t)p->height * p->width > (1 << 26)) return fail(who + ": height and width must be at least 1 (and height * width at most 2^26)");
+  if (!world_ids || n_selected < 1) return fail(who + ": at least one world must be selected");
   std::vector<char> seen((size_t)b->n_worlds, 0);
   for (int i = 0; i < n_selected; ++i) {
-    if (world_ids[i] < 0 || world_ids[i] >= b->n_worlds) return fail("nmf_camera_plan_create: world id " + std::to_string(world_ids[i]) + " is outside [0, " + std::to_string(b->n_worlds) + ")");
-    if (seen[(size_t)world_ids[i]]) return fail("nmf_camera_plan_create: world id " + std::to_string(world_ids[i]) + " is selected twice");
+    if (world_ids[i] < 0 || world_ids[i] >= b->n_worlds) return fail(who + ": world id " + std::to_string(world_ids[i]) + " is outside [0, " + std::to_string(b->n_worlds) + ")");
+    if (seen[(size_t)world_ids[i]]) return fail(who + ": world id " + std::to_string(world_ids[i]) + " is selected twice");
     seen[(size_t)world_ids[i]] = 1;
   }
-  if (n_caps < 0 || n_caps > NMF_CAMERA_MAX_CAPSULES || (n_caps > 0 && (!cap_seg || !cap_geom || !cap_rgb))) return fail("nmf_camera_plan_create: bad capsule list (at most 72)");
-  for (int c = 0; c < n_caps; ++c) {
-    if (cap_seg[c] < 0 || cap_seg[c] >= m->nseg) return fail("nmf_camera_plan_create: capsule segment out of range");
-    if (!(cap_geom[7 * c + 6] > 0.f)) return fail("nmf_camera_plan_create: a capsule needs a positive radius");
+  for (int f = 0; f < n_flies; ++f) {
+    const nmf_camera_fly& F = flies[f];
+    if (F.n_caps < 0 || F.n_caps > NMF_CAMERA_MAX_CAPSULES || (F.n_caps > 0 && (!F.cap_seg || !F.cap_geom || !F.cap_rgb))) return fail(who + ": bad capsule list (at most 72)");
+    for (int c = 0; c < F.n_caps; ++c) {
+      if (F.cap_seg[c] < 0 || F.cap_seg[c] >= F.batch->model->nseg) return fail(who + ": capsule segment out of range");
+      if (!(F.cap_geom[7 * c + 6] > 0.f)) return fail(who + ": a capsule needs a positive radius");
+    }
   }
-  if (p->n_spheres < 0 || p->n_spheres > nmf::kMaxSpheres) return fail("nmf_camera_plan_create: at most 8 spheres");
-  if (!(p->checker_size > 0.f)) return fail("nmf_camera_plan_create: bad checker size");
-  if (!(p->ambient >= 0.f) || !(p->diffuse >= 0.f)) return fail("nmf_camera_plan_create: the light terms must not be negative");
-  if (b->dm.plane[0] != 0.f || b->dm.plane[1] != 0.f || b->dm.plane[2] != 1.f) return fail("nmf_camera_plan_create: the ground plane must be z-up");
+  if (p->n_spheres < 0 || p->n_spheres > nmf::kMaxSpheres) return fail(who + ": at most 8 spheres");
+  if (!(p->checker_size > 0.f)) return fail(who + ": bad checker size");
+  if (!(p->ambient >= 0.f) || !(p->diffuse >= 0.f)) return fail(who + ": the light terms must not be negative");
+  if (b->dm.plane[0] != 0.f || b->dm.plane[1] != 0.f || b->dm.plane[2] != 1.f) return fail(who + ": the ground plane must be z-up");
   std::vector<nmf::CamView> views((size_t)n_cameras);
   for (int c = 0; c < n_cameras; ++c) {
     const nmf_camera_view& v = p->cam[c];
-    if (v.mode != NMF_CAMERA_FIXED && v.mode != NMF_CAMERA_TRACK) return fail("nmf_camera_plan_create: camera mode must be NMF_CAMERA_FIXED or NMF_CAMERA_TRACK");
-    if (v.mode == NMF_CAMERA_TRACK && (v.track_seg < 0 || v.track_seg >= m->nseg)) return fail("nmf_camera_plan_create: tracked segment out of range");
-    if (!(v.fovy_deg > 0.f) || !(v.fovy_deg < 180.f)) return fail("nmf_camera_plan_create: need 0 < fovy < 180 degrees");
+    const int owner = cam_fly ? cam_fly[c] : 0;
+    if (owner < 0 || owner >= n_flies) return fail(who + ": cam_fly[" + std::to_string(c) + "] = " + std::to_string(owner) + " is outside [0, n_flies)");
+    if (v.mode != NMF_CAMERA_FIXED && v.mode != NMF_CAMERA_TRACK) return fail(who + ": camera mode must be NMF_CAMERA_FIXED or NMF_CAMERA_TRACK");
+    if (v.mode == NMF_CAMERA_TRACK && (v.track_seg < 0 || v.track_seg >= flies[owner].batch->model->nseg)) return fail(who + ": tracked segment out of range");
+    if (!(v.fovy_deg > 0.f) || !(v.fovy_deg < 180.f)) return fail(who + ": need 0 < fovy < 180 degrees");
     for (int i = 0; i < 3; ++i)          // orthonormal columns
       for (int j = i; j < 3; ++j) {
         const double dd = (double)v.rot[i] * v.rot[j] + (double)v.rot[3 + i] * v.rot[3 + j] + (double)v.rot[6 + i] * v.rot[6 + j];
-        if (!(std::fabs(dd - (i == j ? 1.0 : 0.0)) < 1e-4)) return fail("nmf_camera_plan_create: the camera rotation must be orthonormal");
+        if (!(std::fabs(dd - (i == j ? 1.0 : 0.0)) < 1e-4)) return fail(who + ": the camera rotation must be orthonormal");
       }
     views[c].mode = v.mode; views[c].seg = v.mode == NMF_CAMERA_TRACK ? v.track_seg : 0;
     for (int i = 0; i < 3; ++i) views[c].pos[i] = v.pos[i];
     for (int i = 0; i < 9; ++i) views[c].rot[i] = v.rot[i];
     views[c].tan_px = (float)(std::tan(0.5 * (double)v.fovy_deg * 3.14159265358979323846 / 180.0) / (0.5 * (double)p->height));
+    P->flies.cam_fly[c] = owner;
   }
   nmf::CamArgs& A = P->args;
   A.height = p->height; A.width = p->width; A.tiles_x = (p->width + nmf::kCamTile - 1) / nmf::kCamTile;
@@ -1064,21 +1077,27 @@ static int fill_camera_plan(nmf_camera_plan* P, const nmf_batch* b, const nmf_ca
   A.n_spheres = p->n_spheres; A.sphere_stride = p->spheres_per_world ? 4 * p->n_spheres : 0;
   A.terrain_kind = p->terrain_relief ? b->dm.terrain_type : 0;
   for (int k = 0; k < 5; ++k) A.terrain[k] = b->dm.terrain[k];
-  A.n_caps = n_caps;
+  A.n_caps = flies[0].n_caps;
   for (int c = 0; c < 4; ++c) {
     A.rgb[0][c] = c < 3 ? p->sky_rgb[c] : 0; A.rgb[1][c] = c < 3 ? p->ground_rgb[0][c] : 0; A.rgb[2][c] = c < 3 ? p->ground_rgb[1][c] : 0;
     A.rgb[3][c] = c < 3 ? p->wall_rgb[c] : 0;
     for (int s = 0; s < nmf::kMaxSpheres; ++s) A.rgb[4 + s][c] = c < 3 ? p->sphere_rgb[s][c] : 0;
   }
-  P->spheres_per_world = p->spheres_per_world != 0;
-  P->n_cameras = n_cameras; P->n_selected = n_selected; P->n_caps = n_caps;
-  std::vector<unsigned int> rgbw((size_t)std::max(n_caps, 1), 0u);
-  for (int c = 0; c < n_caps; ++c) rgbw[(size_t)c] = (unsigned int)cap_rgb[3 * c] | ((unsigned int)cap_rgb[3 * c + 1] << 8) | ((unsigned int)cap_rgb[3 * c + 2] << 16);
+  P->n_cameras = n_cameras; P->n_selected = n_selected;
   P->views = (nmf::CamView*)P->mem.upload(views.data(), sizeof(nmf::CamView) * views.size());
   P->world_ids = (int*)P->mem.upload(world_ids, sizeof(int) * (size_t)n_selected);
-  P->cap_seg = (int*)P->mem.upload(cap_seg, sizeof(int) * (size_t)n_caps);
-  P->cap_geom = (float*)P->mem.upload(cap_geom, sizeof(float) * 7 * (size_t)n_caps);
-  P->cap_rgb = (unsigned int*)P->mem.upload(rgbw.data(), sizeof(unsigned int) * (size_t)n_caps);
+  P->flies.n_flies = n_flies;
+  for (int f = 0; f < n_flies; ++f) {
+    const nmf_camera_fly& F = flies[f];
+    const int n_caps = F.n_caps;
+    std::vector<unsigned int> rgbw((size_t)std::max(n_caps, 1), 0u);
+    for (int c = 0; c < n_caps; ++c) rgbw[(size_t)c] = (unsigned int)F.cap_rgb[3 * c] | ((unsigned int)F.cap_rgb[3 * c + 1] << 8) | ((unsigned int)F.cap_rgb[3 * c + 2] << 16);
+    nmf::CamFly& D = P->flies.fly[f];
+    D.seg_xpos = F.batch->st.seg_xpos; D.seg_xquat = F.batch->st.seg_xquat; D.nseg = F.batch->model->nseg; D.n_caps = n_caps;
+    D.cap_seg = (const int*)P->mem.upload(F.cap_seg, sizeof(int) * (size_t)n_caps);
+    D.cap_geom = (const float*)P->mem.upload(F.cap_geom, sizeof(float) * 7 * (size_t)n_caps);
+    D.cap_rgb = (const unsigned int*)P->mem.upload(rgbw.data(), sizeof(unsigned int) * (size_t)n_caps);
+  }
   if (!P->mem.ok) return -1;
   HIP_OK(hipDeviceSynchronize());
   return 0;
@@ -1089,23 +1108,66 @@ extern "C" nmf_camera_plan* nmf_camera_plan_create(nmf_batch* b, const nmf_camer
   if (!b || !p) { fail("nmf_camera_plan_create: null batch / params"); return nullptr; }
   return build_or_destroy(b->mem.device, "nmf_camera_plan_create", new nmf_camera_plan(), nmf_camera_plan_destroy, [&](nmf_camera_plan* P) {
     P->batch = b;
-    return fill_camera_plan(P, b, p, n_cameras, world_ids, n_selected, cap_seg, cap_geom, cap_rgb, n_caps);
+    const nmf_camera_fly one{b, cap_seg, cap_geom, cap_rgb, n_caps};
+    return fill_camera_plan(P, "nmf_camera_plan_create", &one, 1, p, nullptr, n_cameras, world_ids, n_selected);
   });
+}
+
+extern "C" nmf_camera_plan* nmf_camera_plan_create_flies(const nmf_camera_fly* flies, int n_flies, const nmf_camera_params* p, const int32_t* cam_fly,
+                                                         int n_cameras, const int32_t* world_ids, int n_selected) {
+  const std::string who = "nmf_camera_plan_create_flies";
+  if (!flies || !p || !cam_fly) { fail(who + ": null flies / params / cam_fly"); return nullptr; }
+  if (n_flies < 1 || n_flies > NMF_CAMERA_MAX_FLIES) { fail(who + ": need 1 <= n_flies <= NMF_CAMERA_MAX_FLIES = " + std::to_string(NMF_CAMERA_MAX_FLIES) + ", got " + std::to_string(n_flies)); return nullptr; }
+  for (int f = 0; f < n_flies; ++f)
+    if (!flies[f].batch) { fail(who + ": the batch of fly " + std::to_string(f) + " is null"); return nullptr; }
+  const nmf_batch* b = flies[0].batch;
+  for (int f = 1; f < n_flies; ++f) {
+    const nmf_batch* o = flies[f].batch;
+    const std::string fly = who + ": the batch of fly " + std::to_string(f);
+    if (o->mem.device != b->mem.device) { fail(fly + " is on another device than fly 0's"); return nullptr; }
+    if (o->n_worlds != b->n_worlds) { fail(fly + " has " + std::to_string(o->n_worlds) + " worlds, fly 0's has " + std::to_string(b->n_worlds)); return nullptr; }
+    if (std::memcmp(o->dm.plane, b->dm.plane, sizeof(b->dm.plane)) != 0) { fail(fly + " has another ground plane than fly 0's"); return nullptr; }
+    if (o->dm.terrain_type != b->dm.terrain_type || std::memcmp(o->dm.terrain, b->dm.terrain, sizeof(b->dm.terrain)) != 0) { fail(fly + " has another terrain than fly 0's"); return nullptr; }
+  }
+  return build_or_destroy(b->mem.device, "nmf_camera_plan_create_flies", new nmf_camera_plan(), nmf_camera_plan_destroy, [&](nmf_camera_plan* P) {
+    P->batch = b; P->several = true;
+    return fill_camera_plan(P, who, flies, n_flies, p, cam_fly, n_cameras, world_ids, n_selected);
+  });
+}
+
+static int camera_render_args(const std::string& who, const nmf_camera_plan* P, const float* spheres_dev, const uint8_t* frames_out_dev) {
+  if (!frames_out_dev) return fail(who + ": nothing to write");
+  if (reinterpret_cast<uintptr_t>(frames_out_dev) & 15u) return fail(who + ": frames must be 16-byte aligned");
+  if (P->args.n_spheres > 0 && !spheres_dev) return fail(who + ": the plan has spheres, spheres_dev is required");
+  return 0;
 }
 
 // Pure stream-ordered work: argument checks on the host, one kernel launch.
 extern "C" int nmf_camera_render(nmf_batch* b, const nmf_camera_plan* P, const float* spheres_dev, uint8_t* frames_out_dev, void* stream) {
   if (!b || !P) return fail("nmf_camera_render: null batch / plan");
+  if (P->several) return fail("nmf_camera_render: the plan has several flies: nmf_camera_render_flies");
   if (P->batch != b) return fail("nmf_camera_render: the plan was made for another batch");
-  if (!frames_out_dev) return fail("nmf_camera_render: nothing to write");
-  if (reinterpret_cast<uintptr_t>(frames_out_dev) & 15u) return fail("nmf_camera_render: frames must be 16-byte aligned");
-  if (P->args.n_spheres > 0 && !spheres_dev) return fail("nmf_camera_render: the plan has spheres, spheres_dev is required");
+  if (camera_render_args("nmf_camera_render", P, spheres_dev, frames_out_dev) != 0) return -1;
   DEVICE_GUARD(b);
   const nmf::CamArgs& A = P->args;
+  const nmf::CamFly& F = P->flies.fly[0];
   const unsigned tiles = (unsigned)(A.tiles_x * ((A.height + nmf::kCamTile - 1) / nmf::kCamTile));
   hipLaunchKernelGGL(nmf::nmf_camera_kernel, dim3(tiles, (unsigned)P->n_cameras, (unsigned)P->n_selected), dim3(nmf::kCamThreads), 0, (hipStream_t)stream, A,
-                     P->views, P->world_ids, b->st.seg_xpos, b->st.seg_xquat, b->model->nseg, spheres_dev ? spheres_dev : b->st.seg_xpos,
-                     P->cap_seg, P->cap_geom, P->cap_rgb, frames_out_dev);
+                     P->views, P->world_ids, F.seg_xpos, F.seg_xquat, F.nseg, spheres_dev ? spheres_dev : F.seg_xpos,
+                     F.cap_seg, F.cap_geom, F.cap_rgb, frames_out_dev);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int nmf_camera_render_flies(const nmf_camera_plan* P, const float* spheres_dev, uint8_t* frames_out_dev, void* stream) {
+  if (!P) return fail("nmf_camera_render_flies: null plan");
+  if (!P->several) return fail("nmf_camera_render_flies: the plan has one fly's batch: nmf_camera_render");
+  if (camera_render_args("nmf_camera_render_flies", P, spheres_dev, frames_out_dev) != 0) return -1;
+  DEVICE_GUARD(P->batch);
+  const nmf::CamArgs& A = P->args;
+  const unsigned tiles = (unsigned)(A.tiles_x * ((A.height + nmf::kCamTile - 1) / nmf::kCamTile));
+  hipLaunchKernelGGL(nmf::nmf_camera_flies_kernel, dim3(tiles, (unsigned)P->n_cameras, (unsigned)P->n_selected), dim3(nmf::kCamThreads), 0, (hipStream_t)stream, A,
+                     P->flies, P->views, P->world_ids, spheres_dev ? spheres_dev : P->flies.fly[0].seg_xpos, frames_out_dev);
   HIP_OK(hipGetLastError());
   return 0;
 }

@@ -14,6 +14,10 @@ The reference's GPU class renders selected worlds with MJWarp's batch ray-caster
   with its own colour — lit by one directional light from straight above:
   ``colour = base * (ambient + diffuse * max(0, n_z))``, rounded to uint8.  No shadows, no transparency, no textures.
 
+A world with several flies (one batch per fly) is drawn whole with ``flies="all"`` or a list of fly names: one launch composes
+the drawn flies' batches, the nearest hit wins and, on an exact tie, the earlier object — ground, spheres, then capsules in the
+order (fly, capsule).  :func:`merge_flies` turns flies, cameras and colours into what the library takes, without a GPU.
+
 Frames are uint8 ``(n_selected_worlds, n_cameras, H, W, 3)`` torch tensors that stay on the device until fetched.
 Files are written with Pillow (animated ``.gif`` / ``.png`` / ``.webp``, or a directory of numbered PNGs); other
 containers need ``imageio``, :meth:`show_in_notebook` needs ``mediapy`` — neither is a dependency.
@@ -23,6 +27,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from collections import namedtuple
 from pathlib import Path
 
 import numpy as np
@@ -30,9 +35,11 @@ import numpy as np
 from . import _native
 from .vision import Scene, body_capsules
 
-__all__ = ["HIPBatchRenderer", "CAMERA_MODES", "camera_pose", "resolve_cameras", "grid_shape", "write_video"]
+__all__ = ["HIPBatchRenderer", "CAMERA_MODES", "camera_pose", "resolve_cameras", "select_flies", "merge_flies", "FlyScene", "grid_shape",
+           "write_video"]
 
 CAMERA_MODES = {"fixed": 0, "track": 1}
+MAX_CAMERAS, MAX_FLIES = 8, 4          # NMF_CAMERA_MAX, NMF_CAMERA_MAX_FLIES of include/nmf.h
 PILLOW_SUFFIXES = (".gif", ".png", ".webp")
 
 
@@ -49,6 +56,13 @@ class _CameraParams(ctypes.Structure):
         ("n_spheres", ctypes.c_int32), ("spheres_per_world", ctypes.c_int32),
         ("wall_rgb", ctypes.c_uint8 * 4), ("terrain_relief", ctypes.c_int32),
     ]
+
+
+class _CameraFly(ctypes.Structure):
+    """``nmf_camera_fly`` of include/nmf.h."""
+
+    _fields_ = [("batch", ctypes.c_void_p), ("cap_seg", ctypes.c_void_p), ("cap_geom", ctypes.c_void_p), ("cap_rgb", ctypes.c_void_p),
+                ("n_caps", ctypes.c_int32)]
 
 
 def camera_pose(cam: dict):
@@ -99,6 +113,72 @@ def resolve_cameras(world, cameras) -> list:
             raise ValueError(f"camera '{cam}' {'is ambiguous' if hits else 'not found'}; cameras of this world: {known}")
         out.append(hits[0])
     return out
+
+
+def select_flies(world, flies) -> list:
+    """The names of the flies to draw, in ``world.fly_lookup`` order, for ``flies`` = ``"all"``, a fly name or a list of fly
+    names.  Unknown, repeated or no names: ``ValueError``, as is more than the renderer's limit of flies."""
+    known = list(world.fly_lookup)
+    if isinstance(flies, str):
+        flies = known if flies == "all" else [flies]
+    flies = list(flies)
+    if len(flies) == 0:
+        raise ValueError("At least one fly must be drawn.")
+    for name in flies:
+        if name not in known:
+            raise ValueError(f"fly '{name}' not found; flies of this world: {known}")
+    if len(set(flies)) != len(flies):
+        raise ValueError(f"a fly is repeated in {flies}")
+    if len(flies) > MAX_FLIES:
+        raise ValueError(f"the batch renderer draws at most {MAX_FLIES} flies of a world (NMF_CAMERA_MAX_FLIES), got {len(flies)}")
+    return [name for name in known if name in flies]
+
+
+FlyScene = namedtuple("FlyScene", "fly_names cam_fly track_seg capsule_seg capsule_geom capsule_rgb")
+FlyScene.__doc__ = """What :func:`merge_flies` makes of flies, cameras and colours: ``fly_names`` (the drawn flies in the world's
+order), per camera ``cam_fly`` (index into ``fly_names`` of the fly it belongs to; 0 for a fixed camera of a fly that is not
+drawn) and ``track_seg`` (the tracked segment in that fly's segment order; 0 for fixed cameras), and per drawn fly, in dicts
+by fly name, ``capsule_seg`` (K_f,) int32, ``capsule_geom`` (K_f, 7) float32 and ``capsule_rgb`` (K_f, 3) uint8."""
+
+
+def merge_flies(world, resolved, flies, scene: Scene | None = None, capsule_rgb=None) -> FlyScene:
+    """Flies, cameras and colours of one renderer -> the per-fly arrays and per-camera indices the library takes.  Needs no GPU.
+
+    ``resolved``: what :func:`resolve_cameras` returns; ``flies``: see :func:`select_flies`; ``capsule_rgb``: None, or a dict
+    fly name -> ``(K_f, 3)`` colours in [0, 1] (flies that are missing get ``scene.body_rgb``).  A ``track`` camera follows its
+    own fly, which must be among the drawn ones.  ``ValueError`` for everything that does not fit."""
+    scene = scene or Scene()
+    names = select_flies(world, flies)
+    if len(resolved) > MAX_CAMERAS:
+        raise ValueError(f"at most {MAX_CAMERAS} cameras per renderer")
+    cam_fly, track_seg = [], []
+    for fly, cam in resolved:
+        mode = camera_pose(cam)[0]           # (refuses unsupported modes)
+        if mode == "track" and fly.name not in names:
+            raise ValueError(f"camera '{fly.name}/{cam['name']}' tracks fly '{fly.name}', which is not among the drawn flies {names}")
+        cam_fly.append(names.index(fly.name) if fly.name in names else 0)
+        segs = [s.name for s in fly.get_bodysegs_order()]
+        track_seg.append(segs.index(cam.get("target", fly.root_segment.name)) if mode == "track" else 0)
+    if capsule_rgb is None:
+        capsule_rgb = {}
+    if not isinstance(capsule_rgb, dict):
+        raise ValueError("with several flies capsule_rgb is a dict: fly name -> (K, 3) colours")
+    for name in capsule_rgb:
+        if name not in names:
+            raise ValueError(f"capsule_rgb names fly '{name}', which is not among the drawn flies {names}")
+    seg, geom, rgb = {}, {}, {}
+    for name in names:
+        seg[name], geom[name] = (body_capsules(world.fly_lookup[name], hidden=()) if scene.own_body
+                                 else (np.zeros(0, np.int32), np.zeros((0, 7), np.float32)))
+        k = len(seg[name])
+        if capsule_rgb.get(name) is None:
+            c = np.tile(np.asarray(scene.body_rgb, dtype=np.uint8), (k, 1))
+        else:
+            c = np.floor(np.asarray(capsule_rgb[name], dtype=np.float64).reshape(-1, 3) * 255.0 + 0.5).astype(np.uint8)
+            if len(c) != k:
+                raise ValueError(f"capsule_rgb needs one colour per capsule: ({k}, 3)" + (f" for fly '{name}'" if len(names) > 1 else ""))
+        rgb[name] = np.ascontiguousarray(c.reshape(k, 3))
+    return FlyScene(names, cam_fly, track_seg, seg, geom, rgb)
 
 
 def grid_shape(n_worlds: int) -> tuple:
@@ -280,17 +360,29 @@ class HIPBatchRenderer(_FrameBuffer):
         scene: a :class:`flygym_amd.vision.Scene` (default: the eyes' default scene).
         ambient, diffuse: the light terms.
         capsule_rgb: ``(K, 3)`` colours in [0, 1], one per segment of the fly (default: ``scene.body_rgb`` for all).
+        flies: for a simulation of a world with several flies (:class:`~flygym_amd.simulation.MultiFlyHIPSimulation`, one batch
+            per fly): ``"all"`` or a list of fly names — the flies to draw, always in ``world.fly_lookup`` order, at most 4.
+
+    With ``flies`` the image is composed from all drawn flies' batches in one launch (the nearest hit wins; on an exact tie the
+    earlier fly).  Cameras may then belong to different flies: a ``track`` camera follows its own fly, which must
+    be among the drawn ones.  ``capsule_rgb`` is a dict fly name -> ``(K_f, 3)`` (flies that are missing get
+    ``scene.body_rgb``), and the attributes ``capsule_seg``, ``capsule_geom`` and ``capsule_rgb`` are dicts by fly name.  All
+    batches of such a simulation step together; pacing (:meth:`render_as_needed`) reads the step counter of the FIRST drawn
+    fly's batch.
     """
 
     def __init__(self, sim, cameras, *, worlds=None, camera_res=(240, 320), playback_speed: float = 0.2, output_fps: float = 25,
                  buffer_frames: bool = True, scene: Scene | None = None, ambient: float = 0.4, diffuse: float = 0.6,
-                 capsule_rgb=None):
-        if hasattr(sim, "for_fly"):
-            raise NotImplementedError("worlds with several flies are out of scope for the batch renderer: one batch per fly means "
-                                      "compositing several batches' poses in one image")
+                 capsule_rgb=None, flies=None):
+        several = hasattr(sim, "for_fly")
+        if several and flies is None:
+            raise NotImplementedError("worlds with several flies are drawn on request: pass flies='all' or flies=[fly names] to "
+                                      "compose the image from those flies' batches (one batch per fly)")
+        if not several and flies is not None:
+            raise ValueError("flies= is for a simulation of a world with several flies; this batch steps one fly")
         resolved = resolve_cameras(sim.world, cameras)
-        if len(resolved) > 8:
-            raise ValueError("at most 8 cameras per renderer")
+        if len(resolved) > MAX_CAMERAS:
+            raise ValueError(f"at most {MAX_CAMERAS} cameras per renderer")
         n_worlds = int(sim.n_worlds)
         worlds = list(range(n_worlds)) if worlds is None else [int(w) for w in worlds]
         if len(worlds) == 0:
@@ -303,28 +395,34 @@ class HIPBatchRenderer(_FrameBuffer):
         h, w_ = int(camera_res[0]), int(camera_res[1])
         if h < 1 or w_ < 1:
             raise ValueError(f"camera_res must be (height, width) with both at least 1, got {camera_res}")
-        fly = resolved[0][0]
-        if any(f is not fly for f, _ in resolved):
-            raise NotImplementedError("all cameras of a renderer belong to one fly")
-        names = [s.name for s in fly.get_bodysegs_order()]
-        poses = [camera_pose(cam) for _, cam in resolved]      # (refuses unsupported modes before anything is launched)
+        sc = scene or Scene()
+        if several:
+            merged = merge_flies(sim.world, resolved, flies, sc, capsule_rgb)
+            batches = [sim.for_fly(name) for name in merged.fly_names]
+        else:
+            fly = resolved[0][0]
+            if any(f is not fly for f, _ in resolved):
+                raise NotImplementedError("all cameras of a renderer belong to one fly")
+            merged = merge_flies(sim.world, resolved, [fly.name], sc, None if capsule_rgb is None else {fly.name: capsule_rgb})
+            batches = [sim]
+        poses = [camera_pose(cam) for _, cam in resolved]
         super().__init__(worlds, [f"{f.name}/{cam['name']}" for f, cam in resolved], (h, w_), output_fps, buffer_frames)
-        self.sim, self.scene = sim, scene or Scene()
+        self.sim, self.scene = sim, sc
         self.playback_speed, self.ambient, self.diffuse = float(playback_speed), float(ambient), float(diffuse)
         self._pacer = _Pacer(playback_speed, output_fps)
+        self._paced_by = batches[0]
         self.cameras = [cam for _, cam in resolved]
+        self.fly_names = merged.fly_names if several else None
 
         p = _CameraParams()
         p.height, p.width = h, w_
-        for i, ((_, cam), (mode, pos, mat, fovy)) in enumerate(zip(resolved, poses)):
+        for i, (mode, pos, mat, fovy) in enumerate(poses):
             v = p.cam[i]
-            v.mode, v.fovy_deg = CAMERA_MODES[mode], fovy
-            v.track_seg = names.index(cam.get("target", fly.root_segment.name)) if mode == "track" else 0
+            v.mode, v.fovy_deg, v.track_seg = CAMERA_MODES[mode], fovy, merged.track_seg[i]
             for k in range(3):
                 v.pos[k] = pos[k]
             for k in range(9):
                 v.rot[k] = mat.reshape(9)[k]
-        sc = self.scene
         p.ambient, p.diffuse, p.checker_size = self.ambient, self.diffuse, sc.checker_size
         for i in range(3):
             p.sky_rgb[i], p.wall_rgb[i] = sc.sky_rgb[i], sc.wall_rgb[i]
@@ -332,16 +430,10 @@ class HIPBatchRenderer(_FrameBuffer):
             for s, c in enumerate(sc.sphere_rgb):
                 p.sphere_rgb[s][i] = c[i]
         p.n_spheres, p.spheres_per_world, p.terrain_relief = len(sc.spheres), 0, int(sc.terrain_relief)
-        self.capsule_seg, self.capsule_geom = (body_capsules(fly, hidden=()) if sc.own_body
-                                               else (np.zeros(0, np.int32), np.zeros((0, 7), np.float32)))
-        k = len(self.capsule_seg)
-        if capsule_rgb is None:
-            rgb = np.tile(np.asarray(sc.body_rgb, dtype=np.uint8), (k, 1))
+        if several:
+            self.capsule_seg, self.capsule_geom, self.capsule_rgb = merged.capsule_seg, merged.capsule_geom, merged.capsule_rgb
         else:
-            rgb = np.floor(np.asarray(capsule_rgb, dtype=np.float64).reshape(-1, 3) * 255.0 + 0.5).astype(np.uint8)
-            if len(rgb) != k:
-                raise ValueError(f"capsule_rgb needs one colour per capsule: ({k}, 3)")
-        self.capsule_rgb = np.ascontiguousarray(rgb.reshape(k, 3))
+            self.capsule_seg, self.capsule_geom, self.capsule_rgb = (d[merged.fly_names[0]] for d in merged[3:])
         lib = _native.lib()
         if ctypes.sizeof(_CameraParams) != lib.nmf_camera_params_size():
             raise _native.NativeError("nmf_camera_params layout mismatch between rendering.py and libnmf_hip.so")
@@ -349,10 +441,20 @@ class HIPBatchRenderer(_FrameBuffer):
         t = sim._torch
         self._spheres = t.as_tensor(sc.spheres, device=sim.device) if len(sc.spheres) else None
         ids = np.asarray(worlds, dtype=np.int32)
-        seg, geom = np.ascontiguousarray(self.capsule_seg, dtype=np.int32), np.ascontiguousarray(self.capsule_geom, dtype=np.float32)
-        self._plan_h = lib.nmf_camera_plan_create(sim._batch_h, ctypes.byref(p), len(resolved), ids.ctypes.data, len(ids),
-                                                  seg.ctypes.data if k else None, geom.ctypes.data if k else None,
-                                                  self.capsule_rgb.ctypes.data if k else None, k)
+        records = (_CameraFly * len(batches))()
+        for rec, name, batch in zip(records, merged.fly_names, batches):
+            k = len(merged.capsule_seg[name])
+            rec.batch, rec.n_caps = batch._batch_h, k
+            if k:
+                rec.cap_seg, rec.cap_geom, rec.cap_rgb = (merged[i][name].ctypes.data for i in (3, 4, 5))
+        if several:
+            cam_fly = np.asarray(merged.cam_fly, dtype=np.int32)
+            self._plan_h = lib.nmf_camera_plan_create_flies(records, len(batches), ctypes.byref(p), cam_fly.ctypes.data, len(resolved),
+                                                            ids.ctypes.data, len(ids))
+        else:
+            one = records[0]
+            self._plan_h = lib.nmf_camera_plan_create(one.batch, ctypes.byref(p), len(resolved), ids.ctypes.data, len(ids),
+                                                      one.cap_seg, one.cap_geom, one.cap_rgb, one.n_caps)
         if not self._plan_h:
             msg = lib.nmf_last_error().decode()
             raise ValueError(msg) if "world id" in msg else _native.NativeError(msg)
@@ -398,9 +500,12 @@ class HIPBatchRenderer(_FrameBuffer):
         t = self.sim._torch
         if tuple(out.shape) != self._shape or out.dtype != t.uint8 or out.device != self.sim.device or not out.is_contiguous():
             raise ValueError(f"render_into needs a contiguous uint8 {self._shape} tensor on {self.sim.device}")
-        _native.check(_native.lib().nmf_camera_render(self.sim._batch_h, self._plan_h,
-                                                      self._spheres.data_ptr() if self._spheres is not None else None,
-                                                      out.data_ptr(), self.sim._stream()))
+        spheres = self._spheres.data_ptr() if self._spheres is not None else None
+        lib = _native.lib()
+        if self.fly_names is None:
+            _native.check(lib.nmf_camera_render(self.sim._batch_h, self._plan_h, spheres, out.data_ptr(), self.sim._stream()))
+        else:
+            _native.check(lib.nmf_camera_render_flies(self._plan_h, spheres, out.data_ptr(), self.sim._stream()))
         return out
 
     def render(self):
@@ -413,8 +518,9 @@ class HIPBatchRenderer(_FrameBuffer):
 
     def render_as_needed(self, sim=None) -> bool:
         """Render if a frame is due (first call; then every ``playback_speed / output_fps`` seconds of simulated time, counted
-        from the batch's step counter: no host synchronisation)."""
-        sim = self.sim if sim is None else sim
+        from the batch's step counter: no host synchronisation).  With several flies the counter is that of the first drawn
+        fly's batch: the batches of such a simulation step together."""
+        sim = self._paced_by if sim is None or sim is self.sim else sim
         time_sec = int(_native.lib().nmf_step_count(sim._batch_h)) * sim.timestep
         if not self._pacer.due(time_sec):
             return False

@@ -432,7 +432,8 @@ class HIPSimulation:
 
         ``use_gpu_batch_rendering=True`` builds and returns a :class:`flygym_amd.rendering.HIPBatchRenderer` of the worlds in
         ``worlds`` (default: all) — the counterpart of the reference's ``WarpGPUBatchRenderer``; ``**kwargs`` go to it
-        (``scene``, ``ambient``, ``diffuse``, ``capsule_rgb``).  A ``scene_option`` raises ``RuntimeError`` as the reference's
+        (``scene``, ``ambient``, ``diffuse``, ``capsule_rgb``; ``flies`` for a world with several flies, see
+        :meth:`MultiFlyHIPSimulation.set_renderer`).  A ``scene_option`` raises ``RuntimeError`` as the reference's
         batch renderer does.  ``use_gpu_batch_rendering=False`` is the reference's per-world MuJoCo OpenGL renderer, which
         this engine does not have: ``NotImplementedError``."""
         if not use_gpu_batch_rendering:
@@ -526,6 +527,10 @@ class MultiFlyHIPSimulation(HIPSimulation):
     # ---- fanned out --------------------------------------------------------------------
     def reset(self) -> None:
         for s in self._each(): s.reset()
+        if self.renderer is not None:
+            self.renderer.reset()
+        self._frames_rendered = 0
+        self._total_render_time_ns = 0
 
     def reset_worlds(self, mask) -> None:
         for s in self._each(): s.reset_worlds(mask)
@@ -578,11 +583,17 @@ class MultiFlyHIPSimulation(HIPSimulation):
     def set_leg_adhesion_states(self, fly_name: str, leg_to_adhesion_state) -> None: self.sims[fly_name].set_leg_adhesion_states(fly_name, leg_to_adhesion_state)
     def replay_ids(self, fly_name: str, with_adhesion: bool = False): return self.sims[fly_name].replay_ids(fly_name, with_adhesion)
 
-    # ---- one batch's business ------------------------------------------------------------
-    def set_renderer(self, *args, **kwargs):
-        raise NotImplementedError("worlds with several flies are out of scope for the batch renderer: one batch per fly means "
-                                  "compositing several batches' poses in one image")
+    # ---- rendering: the whole world in one image ------------------------------------------
+    def set_renderer(self, cameras=None, *, flies=None, **kwargs):
+        """:meth:`HIPSimulation.set_renderer` with the same keywords and refusals, and ``flies``: ``"all"`` or a list of fly
+        names — the flies to draw, in ``world.fly_lookup`` order whatever the list's order (unknown, repeated or no names:
+        ``ValueError``).  The renderer composes the drawn flies' batches in one image (``csrc/nmf_camera.hip``: nearest hit, the
+        earlier fly on an exact tie); cameras may belong to different flies, ``capsule_rgb`` is a dict by fly name, and pacing
+        counts the steps of the first drawn fly's batch.  Without ``flies`` a world with several flies is refused
+        (``NotImplementedError``): drawing several flies is asked for by name."""
+        return super().set_renderer(cameras, flies=flies, **kwargs)
 
+    # ---- one batch's business ------------------------------------------------------------
     def _one_batch_only(self, what):
         raise AttributeError(f"{what} belongs to one fly's batch: use sim.for_fly(fly_name).{what} ({', '.join(self.sims)})")
 

@@ -333,6 +333,33 @@ void nmf_camera_plan_destroy(nmf_camera_plan* plan);
  * [n_selected][n_cameras][height][width][3], 16-byte aligned. */
 int nmf_camera_render(nmf_batch* batch, const nmf_camera_plan* plan, const float* spheres_dev, uint8_t* frames_out_dev, void* stream);
 
+/* The same renderer for a world with several flies (reference GPUSimulation.set_renderer draws the whole world, every fly in
+ * it).  One batch per fly (flygym_amd.simulation.MultiFlyHIPSimulation), all of the same n_worlds on one device, world w of
+ * every batch being the same world.  Fly f's capsules take their poses from batch f.  Compositing: the nearest hit wins; on an
+ * exact tie the earlier object does — ground / terrain, spheres, then capsules in the order (fly, capsule) — which is
+ * tests/camera_spec.py with the flies' capsules concatenated. */
+#define NMF_CAMERA_MAX_FLIES 4    /* flies per plan, each with at most NMF_CAMERA_MAX_CAPSULES capsules */
+typedef struct nmf_camera_fly {
+  nmf_batch* batch;             /* the batch that steps this fly                                                         */
+  const int32_t* cap_seg;       /* HOST arrays as for nmf_camera_plan_create: [n_caps], < this batch's segment count     */
+  const float* cap_geom;        /* [n_caps][7]                                                                           */
+  const uint8_t* cap_rgb;       /* [n_caps][3]                                                                           */
+  int32_t n_caps;               /* 0 <= n_caps <= NMF_CAMERA_MAX_CAPSULES                                                */
+} nmf_camera_fly;
+
+/* nmf_camera_plan_create for 1 <= n_flies <= NMF_CAMERA_MAX_FLIES flies.  cam_fly[n_cameras]: the fly (index into `flies`)
+ * whose batch a NMF_CAMERA_TRACK camera follows — its track_seg is a segment of THAT batch; ignored for fixed cameras but
+ * must be in range.  Every check of nmf_camera_plan_create, and: every batch non-null, all on one device, of equal n_worlds,
+ * with the same z-up ground plane and the same terrain kind and parameters.  The plan owns device copies of everything; it
+ * belongs to these batches, which must outlive it.  NOT stream-ordered.  NULL on error (nmf_last_error). */
+nmf_camera_plan* nmf_camera_plan_create_flies(const nmf_camera_fly* flies, int n_flies, const nmf_camera_params* params,
+                                              const int32_t* cam_fly, int n_cameras, const int32_t* world_ids, int n_selected);
+
+/* nmf_camera_render for a plan of nmf_camera_plan_create_flies: argument checks and ONE kernel launch on `stream`, which
+ * must be ordered after the last step of every batch of the plan (the batches of a MultiFlyHIPSimulation are stepped on one
+ * stream).  No allocation, no host synchronisation, hipGraph-capturable as a single node.  Arguments as nmf_camera_render. */
+int nmf_camera_render_flies(const nmf_camera_plan* plan, const float* spheres_dev, uint8_t* frames_out_dev, void* stream);
+
 /* Closed-loop steerable tripod CPG with its state on the device (flygym_amd.controllers.TurningCPG; csrc/nmf_cpg.hip).  No
  * reference counterpart: the snapshot has no CPG (flygym 2.0.1 dropped flygym 1.x's controllers), so this is build-defined
  * (specification tests/cpg_spec.py).  Per world six coupled phase oscillators, legs in the order lf lm lh
