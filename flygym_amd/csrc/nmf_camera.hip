@@ -25,13 +25,15 @@
 // flies' capsules concatenated.  A fly none of whose capsules' covers meets the tile's bounding cone is left out for the whole
 // tile (one workgroup-wide vote after staging it).
 //
-// The terrain cell arithmetic (terrain_cell, floor_int, kTerrainEps, kTerrainWallTol, kMaxTerrainCells) is nmf_eyes.hip's own:
-// this file is compiled after it in the library's translation unit and calls those functions as they are.  The relief walk, the
-// ray-capsule and the ray-sphere arithmetic are written out again here instead of being moved into a shared header: they carry the
-// hit's normal with them, which the eyes do not need, take their discriminants in a better-conditioned form (see `ball` below: the
-// shade of a grazing hit needs it, a material id does not), and the eye frames are pinned pixel for pixel — nmf_eyes.hip stays
-// untouched, and the two copies are not merged into a header.
+// Shared with the eye kernel, one definition each in nmf_scene.h: the relief's cells and the walk of a ray through them (this
+// file's callbacks also record n_z and `lit`), the flat ground hit and rot3.  The staging of the cover discs and of a capsule's
+// end points and the cone-against-disc test (`meets`) are written out in both files; nmf_scene.h says why.  Not shared, on
+// purpose: the ray-sphere and ray-capsule intersections, the pinhole, the capd layout and the tile output.  They carry the hit's
+// normal, which the eyes do not need, and take their discriminants in a better-conditioned form (see `ball` below: the shade of
+// a grazing hit needs it, a material id does not), while the eye frames are pinned pixel for pixel on the textbook form.  This
+// file uses nothing that nmf_eyes.hip defines.
 #include "nmf_device.h"
+#include "nmf_scene.h"
 
 #pragma clang fp reassociate(off)
 
@@ -108,7 +110,6 @@ __device__ __forceinline__ void camera_tile(const CamArgs& A, const CamView* __r
     camp[threadIdx.x] = p;
   }
   __syncthreads();
-  auto uni = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
   const V3 cam = v3(uni(camp[0]), uni(camp[1]), uni(camp[2]));
   float R[9];
 #pragma unroll
@@ -121,8 +122,7 @@ __device__ __forceinline__ void camera_tile(const CamArgs& A, const CamView* __r
     const V3 oc = cam - v3(g[0], g[1], g[2]);
     float* q = sph[s];
     q[0] = -oc.x; q[1] = -oc.y; q[2] = -oc.z; q[3] = r * r; q[4] = 1.0f / r;      // centre - camera
-    unsigned int word; __builtin_memcpy(&word, A.rgb[4 + s], 4);
-    q[5] = __builtin_bit_cast(float, word);
+    q[5] = __builtin_bit_cast(float, rgb_word(A, 4 + s));
     const float dist = sqrtf(dot(oc, oc));
     const float inv = dist > 1e-6f ? 1.0f / dist : 0.f;
     float* c = sphc[s];
@@ -167,8 +167,7 @@ __device__ __forceinline__ void camera_tile(const CamArgs& A, const CamView* __r
   if constexpr (!kFlies) stage(G.fly[0]);
   __syncthreads();
 
-  auto rgb_word = [&](int mtl) { unsigned int v; __builtin_memcpy(&v, A.rgb[mtl], 4); return v; };      // (kernel argument: scalar loads)
-  const unsigned int w_sky = rgb_word(0), w_ga = rgb_word(1), w_gb = rgb_word(2), w_wall = rgb_word(3), w_gx = w_ga ^ w_gb;
+  const unsigned int w_sky = rgb_word(A, 0), w_ga = rgb_word(A, 1), w_gb = rgb_word(A, 2), w_wall = rgb_word(A, 3), w_gx = w_ga ^ w_gb;
   const float inv_cs = 1.0f / A.checker_size;
   const float hz = cam.z - A.ground_z;
   const float cx = 0.5f * (float)A.width, cy = 0.5f * (float)A.height;
@@ -178,7 +177,6 @@ __device__ __forceinline__ void camera_tile(const CamArgs& A, const CamView* __r
   const int lx = lane & 7, ly = lane >> 3;
   uint8_t* const tile_b = reinterpret_cast<uint8_t*>(tile);
 
-  auto to_world = [&](float x, float y, float z) { return v3(R[0] * x + R[1] * y + R[2] * z, R[3] * x + R[4] * y + R[5] * z, R[6] * x + R[7] * y + R[8] * z); };
   // does a cone (axis a, half-angle by cos / sin) meet a disc of angular radius (qc, qs) about the unit direction q?  (nmf_eyes.hip)
   auto meets = [](V3 a, float c_cos, float c_sin, const float* q) {
     const float ca = q[0] * a.x + q[1] * a.y + q[2] * a.z;
@@ -200,7 +198,7 @@ __device__ __forceinline__ void camera_tile(const CamArgs& A, const CamView* __r
     g_raw = g_cos;
     g_cos = fmaxf(g_cos - 1e-5f, 0.f);       // (a patch of a pinhole image spans far less than a right angle)
     g_sin = sqrtf(fmaxf(1.f - g_cos * g_cos, 0.f));
-    gw = to_world(ax_c.x, ax_c.y, ax_c.z);
+    gw = rot3(R, ax_c);
   };
   // culling, lane = object.  Round 1: capsules 0..63; round 2: lanes 0..7 = capsules 64..71, lanes 8..15 = the spheres
   auto cull_lo = [&](V3 gw, float g_cos, float g_sin, int n_caps) {
@@ -225,7 +223,7 @@ __device__ __forceinline__ void camera_tile(const CamArgs& A, const CamView* __r
   auto ray = [&](int row, int col) {
     const float u = ((float)col + 0.5f - cx) * tpx, v = ((float)row + 0.5f - cy) * tpx;
     const float inorm = __builtin_amdgcn_rsqf(u * u + v * v + 1.f);
-    return to_world(u * inorm, -v * inorm, -inorm);
+    return rot3(R, v3(u * inorm, -v * inorm, -inorm));
   };
   // Discriminants in the well-conditioned form: a ray (unit d) passes a point c at the distance |d x c|, so it meets the sphere
   // of radius r about c iff r^2 - |d x c|^2 >= 0 — a difference of two numbers of the size of r^2.  The textbook form
@@ -242,36 +240,14 @@ __device__ __forceinline__ void camera_tile(const CamArgs& A, const CamView* __r
   auto scene = [&](const V3& d, bool grp_ground, unsigned int grp_sph) {
     CamHit h{w_sky, INFINITY, 0.f, false};
     if (grp_ground) {
-      const float t = -hz * __builtin_amdgcn_rcpf(d.z);
-      const bool ghit = d.z < 0.f && t > 0.f;
-      const float gx = (cam.x + t * d.x) * inv_cs, gy = (cam.y + t * d.y) * inv_cs;
-      const unsigned int pm = (unsigned int)(((floor_int(gx) + floor_int(gy)) << 31) >> 31);
-      h.rgb = ghit ? (w_ga ^ (pm & w_gx)) : w_sky;
-      h.tbest = ghit ? t : INFINITY; h.nz = 1.f; h.lit = ghit;
-      if (A.terrain_kind != 0 && d.z < 0.f) {
-        // relief: follow the ray through the cells of h(x, y) from the highest level down (nmf_eyes.hip's walk; a top has
-        // n_z = 1, a side wall n_z = 0)
-        const float rdz = 1.0f / d.z;
-        float tc = fmaxf(0.f, (A.ground_z + A.terrain[4] - cam.z) * rdz);
-#pragma unroll 1
-        for (int it = 0; it < kMaxTerrainCells; ++it) {
-          const float tp = tc + kTerrainEps;
-          const TerrainCell c = terrain_cell(A.terrain_kind, A.terrain, cam.x + tp * d.x, cam.y + tp * d.y);
-          const float hc = c.h + A.ground_z;
-          const float z_in = cam.z + tc * d.z;
-          if (z_in < hc - kTerrainWallTol) { h.tbest = tc; h.rgb = w_wall; h.nz = 0.f; h.lit = true; break; }
-          const float tx = d.x > 0.f ? (c.x1 - cam.x) / d.x : (d.x < 0.f ? (c.x0 - cam.x) / d.x : INFINITY);
-          const float ty = d.y > 0.f ? (c.y1 - cam.y) / d.y : (d.y < 0.f ? (c.y0 - cam.y) / d.y : INFINITY);
-          const float t_out = fminf(tx, ty);
-          const float t_h = (hc - cam.z) * rdz;
-          if (t_h <= t_out) {
-            const float qx = (cam.x + t_h * d.x) * inv_cs, qy = (cam.y + t_h * d.y) * inv_cs;
-            h.tbest = t_h; h.rgb = ((floor_int(qx) + floor_int(qy)) & 1) ? w_gb : w_ga; h.nz = 1.f; h.lit = true;
-            break;
-          }
-          tc = t_out;
-        }
-      }
+      const GroundHit g = ground_hit(cam, hz, inv_cs, d);
+      h.rgb = g.hit ? (w_ga ^ (g.odd & w_gx)) : w_sky;
+      h.tbest = g.hit ? g.t : INFINITY; h.nz = 1.f; h.lit = g.hit;
+      // the relief instead, where the world has one: a top has n_z = 1, a side wall n_z = 0
+      if (A.terrain_kind != 0 && d.z < 0.f)
+        relief_walk(A.terrain_kind, A.terrain, A.ground_z, cam, inv_cs, d,
+                    [&](float t) { h.tbest = t; h.rgb = w_wall; h.nz = 0.f; h.lit = true; },
+                    [&](float t, bool odd) { h.tbest = t; h.rgb = odd ? w_gb : w_ga; h.nz = 1.f; h.lit = true; });
     }
     for (unsigned int sm = grp_sph; sm; sm &= sm - 1u) {
       const int s = __ffs((int)sm) - 1;

@@ -19,6 +19,9 @@
 #include "nmf_batch_ops.hip"
 #include "nmf_step.hip"
 #include "nmf_sensors.hip"
+// `#pragma clang fp reassociate(off)` at file scope holds from the first file that sets it to the end of the translation unit:
+// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip and the host code below are all
+// compiled under it, and the files above are not.  Which files it covers decides their kernels' arithmetic: keep the order.
 #include "nmf_eyes.hip"
 #include "nmf_camera.hip"
 #include "nmf_replay.hip"
@@ -936,6 +939,23 @@ extern "C" nmf_eye_plan* nmf_eye_plan_create(const int16_t* id_map_dev, const vo
   });
 }
 
+// The scene part of a renderer's kernel arguments (nmf::EyeArgs, nmf::CamArgs; nmf_scene.h draws it) from its public parameters
+// (nmf_eye_params, nmf_camera_params: the same field names): checker, ground height, spheres, the relief the physics of batch b
+// collides with, and the rgb table — 0 sky, 1 / 2 ground, 3 terrain side wall, the spheres from `first_sphere` on (everything else of
+// the table 0: the caller fills the slots between afterwards).  Each caller keeps its own checks and error texts.
+template <class Args, class Params>
+void fill_scene(Args& A, const Params& p, const nmf_batch* b, int first_sphere) {
+  A.checker_size = p.checker_size; A.ground_z = b->dm.plane[3];
+  A.n_spheres = p.n_spheres; A.sphere_stride = p.spheres_per_world ? 4 * p.n_spheres : 0;
+  A.terrain_kind = p.terrain_relief ? b->dm.terrain_type : 0;
+  for (int k = 0; k < 5; ++k) A.terrain[k] = b->dm.terrain[k];
+  std::memset(A.rgb, 0, sizeof(A.rgb));          // (the kernels load a material as a whole word: the fourth bytes are 0)
+  for (int c = 0; c < 3; ++c) {
+    A.rgb[0][c] = p.sky_rgb[c]; A.rgb[1][c] = p.ground_rgb[0][c]; A.rgb[2][c] = p.ground_rgb[1][c]; A.rgb[3][c] = p.wall_rgb[c];
+    for (int s = 0; s < nmf::kMaxSpheres; ++s) A.rgb[first_sphere + s][c] = p.sphere_rgb[s][c];
+  }
+}
+
 // Pure stream-ordered work: argument checks on the host, one kernel launch.  Everything the kernel reads besides the batch's poses and
 // the caller's sphere / capsule lists belongs to the plan.
 extern "C" int nmf_eye_render_planned(nmf_batch* b, const nmf_eye_params* p, const nmf_eye_plan* plan, const float* spheres_dev,
@@ -974,16 +994,9 @@ extern "C" int nmf_eye_render_planned(nmf_batch* b, const nmf_eye_params* p, con
                          2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)};
     for (int i = 0; i < 9; ++i) A.rel_mat[e][i] = (float)R[i];
   }
-  A.checker_size = p->checker_size; A.ground_z = b->dm.plane[3];
-  A.n_spheres = p->n_spheres; A.sphere_stride = p->spheres_per_world ? 4 * p->n_spheres : 0;
+  fill_scene(A, *p, b, 5);
   A.n_caps = p->n_capsules;
-  A.terrain_kind = p->terrain_relief ? b->dm.terrain_type : 0;          // the relief the physics of this batch collides with
-  for (int k = 0; k < 5; ++k) A.terrain[k] = b->dm.terrain[k];
-  for (int c = 0; c < 4; ++c) {
-    A.rgb[0][c] = c < 3 ? p->sky_rgb[c] : 0; A.rgb[1][c] = c < 3 ? p->ground_rgb[0][c] : 0; A.rgb[2][c] = c < 3 ? p->ground_rgb[1][c] : 0;
-    A.rgb[3][c] = c < 3 ? p->wall_rgb[c] : 0; A.rgb[4][c] = c < 3 ? p->body_rgb[c] : 0;
-    for (int s = 0; s < nmf::kMaxSpheres; ++s) A.rgb[5 + s][c] = c < 3 ? p->sphere_rgb[s][c] : 0;
-  }
+  for (int c = 0; c < 3; ++c) A.rgb[4][c] = p->body_rgb[c];
   if (p->rays_per_ommatidium != 0 && p->rays_per_ommatidium != nmf::kEyeRays) return fail("nmf_eye_render: rays_per_ommatidium must be 0 (every pixel) or 16");
   if (p->rays_per_ommatidium != 0 && frames_out_dev) return fail("nmf_eye_render: the sampled mode renders no frames (rays_per_ommatidium = 0 does)");
   A.sampled = p->rays_per_ommatidium;
@@ -1073,16 +1086,8 @@ static int fill_camera_plan(nmf_camera_plan* P, const std::string& who, const nm
   nmf::CamArgs& A = P->args;
   A.height = p->height; A.width = p->width; A.tiles_x = (p->width + nmf::kCamTile - 1) / nmf::kCamTile;
   A.ambient = p->ambient; A.diffuse = p->diffuse;
-  A.checker_size = p->checker_size; A.ground_z = b->dm.plane[3];
-  A.n_spheres = p->n_spheres; A.sphere_stride = p->spheres_per_world ? 4 * p->n_spheres : 0;
-  A.terrain_kind = p->terrain_relief ? b->dm.terrain_type : 0;
-  for (int k = 0; k < 5; ++k) A.terrain[k] = b->dm.terrain[k];
+  fill_scene(A, *p, b, 4);
   A.n_caps = flies[0].n_caps;
-  for (int c = 0; c < 4; ++c) {
-    A.rgb[0][c] = c < 3 ? p->sky_rgb[c] : 0; A.rgb[1][c] = c < 3 ? p->ground_rgb[0][c] : 0; A.rgb[2][c] = c < 3 ? p->ground_rgb[1][c] : 0;
-    A.rgb[3][c] = c < 3 ? p->wall_rgb[c] : 0;
-    for (int s = 0; s < nmf::kMaxSpheres; ++s) A.rgb[4 + s][c] = c < 3 ? p->sphere_rgb[s][c] : 0;
-  }
   P->n_cameras = n_cameras; P->n_selected = n_selected;
   P->views = (nmf::CamView*)P->mem.upload(views.data(), sizeof(nmf::CamView) * views.size());
   P->world_ids = (int*)P->mem.upload(world_ids, sizeof(int) * (size_t)n_selected);

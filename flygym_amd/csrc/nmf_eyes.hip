@@ -19,11 +19,13 @@
 // the chunk's run sums; three integer LDS atomics per chunk.  The 1.4 MB raw frame per fly never exists unless the caller asks for it
 // (frames_out, for inspection and for the parity tests): compute-bound instead of HBM-bound.
 #include "nmf_device.h"
+#include "nmf_scene.h"      // the scene's pieces shared with nmf_camera.hip
 
 // The two instantiations of the kernel below (pixel-exact, sampled) must colour a pixel identically — the sampled mode's readings
 // equal its specification applied to the pixel-exact mode's frames bit for bit (tests/test_sensors.py) — so the ray and scene
 // arithmetic may not be re-associated differently in the two contexts (the library is built with -fassociative-math).  Fused
-// multiply-adds stay (contraction does not depend on the surrounding code).
+// multiply-adds stay (contraction does not depend on the surrounding code).  nmf_scene.h states the same pragma for its pieces and
+// the rule that follows from it: nothing on a ray's path comes from a header compiled without it.
 #pragma clang fp reassociate(off)
 
 namespace nmf {
@@ -34,11 +36,7 @@ __device__ unsigned long long g_eye_stats[8];
 constexpr int kEyeThreads = 256;
 constexpr int kEyeRays = 16;        // rays per ommatidium of the sampled mode: one DPP row of lanes
 constexpr int kEyeSlots = 16;       // ommatidia per group of the sampled mode (a 4 x 4 patch of the lattice: one culling for 256 rays)
-constexpr int kMaxSpheres = 8;
 constexpr int kMaxCaps = 64;            // capsules of the fly's own body an eye can see
-constexpr int kMaxTerrainCells = 64;    // cells a ray is followed through the relief before the far field is taken as flat
-constexpr float kTerrainEps = 1e-4f;    // the cell a ray is in at parameter t holds its point at t + eps (mm)
-constexpr float kTerrainWallTol = 1e-4f;   // entered through the side wall: this far below the cell's level (levels differ by >= 0.3 mm)
 
 struct EyeArgs {
   int height, width;
@@ -55,35 +53,6 @@ struct EyeArgs {
   unsigned char rgb[5 + kMaxSpheres][4];   // materials: 0 sky, 1 ground A, 2 ground B, 3 terrain side wall, 4 own body, 5.. spheres
 };
 
-// constant-height cell of h(x, y) that holds (x, y): bounds (+-inf where unbounded) and level — the same arithmetic as
-// the physics' terrain_height (nmf_step_collision.h) and as oracle/sensors_oracle.py::terrain_cell
-struct TerrainCell { float x0, x1, y0, y1, h; };
-__device__ __forceinline__ TerrainCell cell_gapped(float block, float gap, float depth, float x) {
-  const float period = block + gap;
-  const float base = floorf(x / period) * period;
-  const bool on = x - base < block;
-  return TerrainCell{on ? base : base + block, on ? base + block : base + period, -INFINITY, INFINITY, on ? 0.f : -depth};
-}
-__device__ __forceinline__ TerrainCell cell_blocks(float size, float height, float x, float y) {
-  const float i = floorf(x / size), j = floorf(y / size);
-  const float sum = i + j;
-  const float par = sum - 2.f * floorf(sum / 2.f);
-  return TerrainCell{i * size, (i + 1.f) * size, j * size, (j + 1.f) * size, par != 0.f ? height : 0.f};
-}
-__device__ __forceinline__ TerrainCell terrain_cell(int kind, const float* p, float x, float y) {
-  if (kind == 1) return cell_gapped(p[0], p[1], p[2], x);
-  if (kind == 2) return cell_blocks(p[0], p[1], x, y);
-  if (kind == 3) {
-    const float st = floorf(x / p[3]);
-    const float k = st - 3.f * floorf(st / 3.f);
-    const float s0 = st * p[3], s1 = (st + 1.f) * p[3];
-    if (k == 1.f) { TerrainCell c = cell_gapped(1.0f, p[1], p[2], x); c.x0 = fmaxf(c.x0, s0); c.x1 = fminf(c.x1, s1); return c; }
-    if (k == 2.f) { TerrainCell c = cell_blocks(p[0], 0.35f, x, y); c.x0 = fmaxf(c.x0, s0); c.x1 = fminf(c.x1, s1); return c; }
-    return TerrainCell{s0, s1, -INFINITY, INFINITY, 0.f};
-  }
-  return TerrainCell{-INFINITY, INFINITY, -INFINITY, INFINITY, 0.f};
-}
-
 // camera-frame ray of a raw pixel (equidistant fisheye).  (A per-pixel ray table shared by all worlds was tried: 16 B
 // per ray through L2 is slower than recomputing the lens model, 5.5 vs 2.4 ms per 8192 eye views.)
 __device__ __forceinline__ V3 eye_ray(int row, int col, float cx, float cy, float inv_half_h, float half_fov, float& theta) {
@@ -93,13 +62,6 @@ __device__ __forceinline__ V3 eye_ray(int row, int col, float cx, float cy, floa
   theta = rho2 * rinv * half_fov;
   const float st = __sinf(theta), ct = __cosf(theta);
   return v3(st * u * rinv, -st * v * rinv, -ct);          // x right, y up, looks along -z
-}
-
-// floor(x) as an integer in one instruction (saturating, NaN -> 0: no guard needed for rays that miss)
-__device__ __forceinline__ int floor_int(float x) {
-  int r;
-  asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(r) : "v"(x));
-  return r;
 }
 
 // sin(theta) / theta and cos(theta) as polynomials in x = theta^2 for theta <= 2.1 (a lens up to 240 degrees): near-minimax fits of
@@ -149,8 +111,7 @@ nmf_eye_kernel(EyeArgs A, const float* __restrict__ seg_xpos, const float* __res
     mats[threadIdx.x] = threadIdx.x == 0 ? 0u : *reinterpret_cast<const unsigned int*>(A.rgb[threadIdx.x - 1]);
   __syncthreads();
   // the common materials' rgb words, wave-uniform: scalar registers
-  auto rgb_word = [&](int mtl) { unsigned int v; __builtin_memcpy(&v, A.rgb[mtl], 4); return v; };      // (kernel argument: a scalar load)
-  const unsigned int w_sky = rgb_word(0), w_ga = rgb_word(1), w_gb = rgb_word(2), w_wall = rgb_word(3), w_body = rgb_word(4), w_gx = w_ga ^ w_gb;
+  const unsigned int w_sky = rgb_word(A, 0), w_ga = rgb_word(A, 1), w_gb = rgb_word(A, 2), w_wall = rgb_word(A, 3), w_body = rgb_word(A, 4), w_gx = w_ga ^ w_gb;
   // camera pose (uniform over the workgroup)
   const int sg = A.eye_seg[eye];
   float Rs[9];
@@ -164,7 +125,6 @@ nmf_eye_kernel(EyeArgs A, const float* __restrict__ seg_xpos, const float* __res
       R[3 * i + j] = Rs[3 * i] * A.rel_mat[eye][j] + Rs[3 * i + 1] * A.rel_mat[eye][3 + j] + Rs[3 * i + 2] * A.rel_mat[eye][6 + j];
   // the view's constants are the same in every lane: scalar registers (they took 16 of the pixel loop's 72 vector registers,
   // and 24 more values went to scratch)
-  auto uni = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
 #pragma unroll
   for (int i = 0; i < 9; ++i) R[i] = uni(R[i]);
   const V3 cam = v3(uni(cam_v.x), uni(cam_v.y), uni(cam_v.z));
@@ -234,8 +194,7 @@ nmf_eye_kernel(EyeArgs A, const float* __restrict__ seg_xpos, const float* __res
     V3 gw[2]; float g_cos[2], g_sin[2];
 #pragma unroll
     for (int pc = 0; pc < 2; ++pc) {
-      const float ax = cn[4 * pc], ay = cn[4 * pc + 1], az = cn[4 * pc + 2];
-      gw[pc] = v3(R[0] * ax + R[1] * ay + R[2] * az, R[3] * ax + R[4] * ay + R[5] * az, R[6] * ax + R[7] * ay + R[8] * az);
+      gw[pc] = rot3(R, v3(cn[4 * pc], cn[4 * pc + 1], cn[4 * pc + 2]));
       g_cos[pc] = cn[4 * pc + 3]; g_sin[pc] = sqrtf(fmaxf(1.f - g_cos[pc] * g_cos[pc], 0.f));
     }
     // does a cone (axis a, half-angle by cos / sin) meet a disc of angular radius (qc, qs) about the unit direction q?
@@ -284,7 +243,7 @@ nmf_eye_kernel(EyeArgs A, const float* __restrict__ seg_xpos, const float* __res
       for (int pc = 0; pc < 2; ++pc) {
         if (pc == 1 && !two) break;
         const float4 cc = chunk_cones[(grp * 64 + lane) * 2 + pc];          // bounding cone of the piece's rays, camera frame
-        cw[pc] = v3(R[0] * cc.x + R[1] * cc.y + R[2] * cc.z, R[3] * cc.x + R[4] * cc.y + R[5] * cc.z, R[6] * cc.x + R[7] * cc.y + R[8] * cc.z);
+        cw[pc] = rot3(R, v3(cc.x, cc.y, cc.z));
         c_cos[pc] = cc.w; c_sin[pc] = sqrtf(fmaxf(1.f - cc.w * cc.w, 0.f));
       }
       for (unsigned long long gm = grp_caps; gm; gm &= gm - 1ull) {
@@ -315,24 +274,20 @@ nmf_eye_kernel(EyeArgs A, const float* __restrict__ seg_xpos, const float* __res
       unsigned int rgb = w_sky;
       float tbest = INFINITY;
       if (grp_ground) {
-        const float t = -hz * __builtin_amdgcn_rcpf(d.z);
-        const bool ghit = d.z < 0.f && t > 0.f;
-        const float gx = (cam.x + t * d.x) * inv_cs, gy = (cam.y + t * d.y) * inv_cs;
-        // checker parity as a mask (bit 0 of the cell sum, sign-extended): ground A xor (mask and (A xor B)) — no select between two scalars
-        const unsigned int pm = (unsigned int)(((floor_int(gx) + floor_int(gy)) << 31) >> 31);
-        rgb = ghit ? (w_ga ^ (pm & w_gx)) : w_sky;
-        if (objs) tbest = ghit ? t : INFINITY;
+        const GroundHit g = ground_hit(cam, hz, inv_cs, d);
+        rgb = g.hit ? (w_ga ^ (g.odd & w_gx)) : w_sky;
+        if (objs) tbest = g.hit ? g.t : INFINITY;
       }
       if (!objs) return rgb;
       if constexpr (RELIEF) if (grp_ground && A.terrain_kind != 0 && d.z < 0.f) {
-        // relief: follow the ray through the cells of h(x, y) from the highest level down; a cell entered below its level
-        // is a side wall, else its top is hit if the ray reaches the level before leaving the cell
+        // relief: nmf_scene.h's relief_walk (which the camera calls) written out — called with two callbacks it costs the
+        // <false, true, true> instantiation a nineteenth spilled register and 4 bytes of scratch (profiles/scene_header_digests.txt)
         const float rdz = 1.0f / d.z;
         float tc = fmaxf(0.f, (A.ground_z + A.terrain[4] - cam.z) * rdz);
 #pragma unroll 1
         for (int it = 0; it < kMaxTerrainCells; ++it) {
           const float tp = tc + kTerrainEps;
-          const TerrainCell c = terrain_cell(A.terrain_kind, A.terrain, cam.x + tp * d.x, cam.y + tp * d.y);
+          const TerrainCell c = relief_cell(A.terrain_kind, A.terrain, cam.x + tp * d.x, cam.y + tp * d.y);
           const float h = c.h + A.ground_z;
           const float z_in = cam.z + tc * d.z;
           if (z_in < h - kTerrainWallTol) { tbest = tc; rgb = w_wall; break; }
@@ -397,7 +352,7 @@ nmf_eye_kernel(EyeArgs A, const float* __restrict__ seg_xpos, const float* __res
         const int pxw_cur = pxw, slw_cur = slw;
         if (grp_caps) {      // the capsules this TURN's 64 rays can meet (wave-uniform: lane = capsule, as for the group)
           const float4 tcn = chunk_cones[__builtin_amdgcn_readfirstlane(grp * (kEyeSlots / 4) + turn)];
-          const V3 tw = v3(R[0] * tcn.x + R[1] * tcn.y + R[2] * tcn.z, R[3] * tcn.x + R[4] * tcn.y + R[5] * tcn.z, R[6] * tcn.x + R[7] * tcn.y + R[8] * tcn.z);
+          const V3 tw = rot3(R, v3(tcn.x, tcn.y, tcn.z));
           const float t_cos = tcn.w, t_sin = sqrtf(fmaxf(1.f - tcn.w * tcn.w, 0.f));
           int sees = 0;
           if (lane < A.n_caps) {
@@ -435,9 +390,7 @@ nmf_eye_kernel(EyeArgs A, const float* __restrict__ seg_xpos, const float* __res
           } else {
             float theta;
             const V3 dc = eye_ray(prow, pcol, cx, cy, inv_half_h, A.half_fov, theta);
-            const float dx = dc.x, dy = dc.y, dz = dc.z;
-            const V3 d = v3(R[0] * dx + R[1] * dy + R[2] * dz, R[3] * dx + R[4] * dy + R[5] * dz, R[6] * dx + R[7] * dy + R[8] * dz);
-            rgbw = scene(d);
+            rgbw = scene(rot3(R, dc));
             rgbw = theta > 3.14159265f ? 0u : rgbw;
           }
           val = is_pale ? ((rgbw >> 16) & 0xffu) : ((rgbw >> 8) & 0xffu);
@@ -534,9 +487,7 @@ nmf_eye_kernel(EyeArgs A, const float* __restrict__ seg_xpos, const float* __res
       for (int k = 0; k < 16; ++k) {
         float theta;
         const V3 dc = eye_ray(row, col, cx, cy, inv_half_h, A.half_fov, theta);
-        const float dx = dc.x, dy = dc.y, dz = dc.z;
-        const V3 d = v3(R[0] * dx + R[1] * dy + R[2] * dz, R[3] * dx + R[4] * dy + R[5] * dz, R[6] * dx + R[7] * dy + R[8] * dz);
-        unsigned int rgbw = scene(d);
+        unsigned int rgbw = scene(rot3(R, dc));
         rgbw = theta > 3.14159265f ? 0u : rgbw;                                // behind the fisheye's full sphere: black
         const unsigned int val = ((pl.z >> k) & 1u) ? ((rgbw >> 16) & 0xffu) : ((rgbw >> 8) & 0xffu);
         if (planned) {
