@@ -174,6 +174,14 @@ def lib():
             "nmf_cpg_hybrid_params_size": (ctypes.c_size_t, []),
             "nmf_cpg_hybrid_enable": (ci, [vp, vp, vp, vp, ci, vp]),
             "nmf_cpg_advance_hybrid": (ci, [vp, ci, vp, ci, vp]),
+            "nmf_plume_params_size": (ctypes.c_size_t, []),
+            "nmf_plume_create": (vp, [vp, vp, vp, vp]),
+            "nmf_plume_destroy": (None, [vp]),
+            "nmf_plume_reset": (ci, [vp, vp, vp]),
+            "nmf_plume_advance": (ci, [vp, ci, vp]),
+            "nmf_plume_field_ptr": (vp, [vp, ci, ctypes.POINTER(ctypes.c_int32)]),
+            "nmf_plume_sample_points": (ci, [vp, vp, ci, vp, vp, vp]),
+            "nmf_plume_sample_sites": (ci, [vp, vp, vp, ci, vp, vp, vp]),
             "nmf_odor_intensity": (ci, [vp, vp, vp, ci, vp, vp, ci, ci, vp, vp]),
             "nmf_replay_resample": (ci, [vp, ci, ci, ctypes.c_double, ctypes.c_double, vp, ci, ci, vp, vp]),
         }

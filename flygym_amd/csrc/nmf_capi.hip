@@ -20,12 +20,13 @@
 #include "nmf_step.hip"
 #include "nmf_sensors.hip"
 // `#pragma clang fp reassociate(off)` at file scope holds from the first file that sets it to the end of the translation unit:
-// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip and the host code below are all
+// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip, nmf_plume.hip and the host code below are all
 // compiled under it, and the files above are not.  Which files it covers decides their kernels' arithmetic: keep the order.
 #include "nmf_eyes.hip"
 #include "nmf_camera.hip"
 #include "nmf_replay.hip"
 #include "nmf_cpg.hip"
+#include "nmf_plume.hip"
 #include "nmf_skeleton.h"      // nmf_model, the blob parser, classify_skeleton
 #endif
 
@@ -58,7 +59,7 @@ struct DeviceGuard {
   DeviceGuard guard_((b)->mem.device);                                                        \
   if (guard_.err != hipSuccess) return fail(std::string("hipSetDevice: ") + hipGetErrorString(guard_.err))
 
-// The device memory of one handle (batch, eye plan, camera plan, CPG): every allocation is 16-byte granular, recorded, and freed
+// The device memory of one handle (batch, eye plan, camera plan, CPG, plume): every allocation is 16-byte granular, recorded, and freed
 // with the handle.  The first failure sets the error text, named after the entry point `who`, and sticks: later calls return
 // null without touching the device, so that a caller tests `ok` once after its last allocation.
 struct DevMem {
@@ -1380,6 +1381,135 @@ extern "C" int nmf_cpg_hybrid_enable(nmf_cpg* C, const nmf_cpg_hybrid_params* p,
 
 extern "C" int nmf_cpg_advance_hybrid(nmf_cpg* C, int n_steps, float* table_dev, int table_steps, void* stream) {
   return cpg_advance("nmf_cpg_advance_hybrid", true, C, n_steps, table_dev, table_steps, stream);
+}
+
+// ---- advected odor plumes (nmf_plume.hip) ----
+// The shared maps (own device copies) and the per-plume state; the batch lends its pose arrays to nmf_plume_sample_sites.
+struct nmf_plume {
+  const nmf_batch* batch = nullptr;
+  int n_worlds = 0;
+  nmf::PlumeArgs args{};
+  float* source = nullptr; float* eddies = nullptr;
+  float* grid[2] = {nullptr, nullptr}; float* wind = nullptr; unsigned int* ticks = nullptr; int* parity = nullptr;
+  DevMem mem;
+};
+
+extern "C" size_t nmf_plume_params_size(void) { return sizeof(nmf_plume_params); }
+
+extern "C" void nmf_plume_destroy(nmf_plume* P) {
+  if (!P) return;
+  P->mem.release();
+  delete P;
+}
+
+extern "C" int nmf_plume_reset(nmf_plume* P, const uint8_t* mask_dev, void* stream) {
+  if (!P) return fail("nmf_plume_reset: null plume");
+  DEVICE_GUARD(P);
+  const size_t total = (size_t)P->args.n_plumes * (size_t)P->args.H * (size_t)P->args.W;
+  hipLaunchKernelGGL(nmf::nmf_plume_reset_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     P->args, mask_dev, P->grid[0], P->grid[1], P->wind, P->ticks);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+static int fill_plume(nmf_plume* P, const nmf_plume_params* p, const float* source, const float* eddies) {
+  if (p->n_plumes != 1 && p->n_plumes != P->n_worlds)
+    return fail("nmf_plume_create: n_plumes must be 1 or the batch's n_worlds (" + std::to_string(P->n_worlds) + "), got " + std::to_string(p->n_plumes));
+  if (p->height < 8 || p->height > 1024 || p->width < 8 || p->width > 1024)
+    return fail("nmf_plume_create: need 8 <= height, width <= 1024 cells, got " + std::to_string(p->height) + " x " + std::to_string(p->width));
+  if (p->first_world < 0) return fail("nmf_plume_create: first_world must not be negative");
+  const float values[11] = {p->cell_size, p->origin_x, p->origin_y, p->tick_s, p->diffusivity, p->mean_wind_x, p->mean_wind_y, p->wind_tau,
+                            p->wind_sigma, p->eddy_gain, p->intensity_scale};
+  for (float v : values)
+    if (!std::isfinite(v)) return fail("nmf_plume_create: a parameter is not finite");
+  if (!(p->cell_size > 0.f) || !(p->tick_s > 0.f) || !(p->wind_tau > 0.f))
+    return fail("nmf_plume_create: cell_size, tick_s and wind_tau must be positive");
+  if (p->diffusivity < 0.f || p->wind_sigma < 0.f) return fail("nmf_plume_create: diffusivity and wind_sigma must not be negative");
+  const double h = p->cell_size, dt = p->tick_s, D = (double)p->diffusivity * dt / (h * h);
+  if (D > 0.25) return fail("nmf_plume_create: diffusivity tick_s / cell_size^2 = " + std::to_string(D) + " exceeds 1/4 (the explicit diffusion step is unstable)");
+  if (!source) return fail("nmf_plume_create: the source map is required");
+  const size_t cells = (size_t)p->height * (size_t)p->width, n = (size_t)p->n_plumes;
+  for (size_t c = 0; c < cells; ++c)
+    if (!std::isfinite(source[c])) return fail("nmf_plume_create: source[" + std::to_string(c) + "] is not finite");
+  for (size_t c = 0; eddies && c < 2 * cells; ++c)
+    if (!std::isfinite(eddies[c])) return fail("nmf_plume_create: eddies[" + std::to_string(c) + "] is not finite");
+  nmf::PlumeArgs& A = P->args;
+  A.n_plumes = p->n_plumes; A.H = p->height; A.W = p->width; A.first_world = p->first_world;
+  A.x0 = p->origin_x; A.y0 = p->origin_y; A.h = p->cell_size; A.scale = p->intensity_scale;
+  A.r = (float)(dt / h); A.D = (float)D; A.eddy_gain = p->eddy_gain;
+  A.a = (float)(dt / (double)p->wind_tau); A.b = (float)((double)p->wind_sigma * std::sqrt(dt));
+  A.mean_x = p->mean_wind_x; A.mean_y = p->mean_wind_y; A.seed = p->seed;
+  P->source = (float*)P->mem.upload(source, sizeof(float) * cells);
+  if (eddies) P->eddies = (float*)P->mem.upload(eddies, sizeof(float) * 2 * cells);
+  for (float*& g : P->grid) g = (float*)P->mem.alloc(sizeof(float) * n * cells);
+  P->wind = (float*)P->mem.alloc(sizeof(float) * 2 * n);
+  P->ticks = (unsigned int*)P->mem.alloc(sizeof(unsigned int) * n);
+  P->parity = (int*)P->mem.alloc(sizeof(int));
+  if (!P->mem.ok) return -1;
+  if (nmf_plume_reset(P, nullptr, nullptr) != 0) return -1;
+  HIP_OK(hipDeviceSynchronize());
+  return 0;
+}
+
+extern "C" nmf_plume* nmf_plume_create(nmf_batch* b, const nmf_plume_params* p, const float* source, const float* eddies) {
+  if (!b || !p) { fail("nmf_plume_create: null batch / params"); return nullptr; }
+  return build_or_destroy(b->mem.device, "nmf_plume_create", new nmf_plume(), nmf_plume_destroy, [&](nmf_plume* P) {
+    P->n_worlds = b->n_worlds; P->batch = b;
+    return fill_plume(P, p, source, eddies);
+  });
+}
+
+extern "C" void* nmf_plume_field_ptr(nmf_plume* P, int which, int32_t* width) {
+  if (!P) { fail("nmf_plume_field_ptr: null plume"); return nullptr; }
+  void* ptr[5] = {P->wind, P->ticks, P->grid[0], P->grid[1], P->parity};
+  const int32_t w[5] = {2, 1, P->args.H * P->args.W, P->args.H * P->args.W, 1};
+  if (which < 0 || which > 4) { fail("nmf_plume_field_ptr: no such field"); return nullptr; }
+  if (width) *width = w[which];
+  return ptr[which];
+}
+
+// Pure stream-ordered work: per tick the grids from the old ones, then winds, tick counters and the parity word.
+extern "C" int nmf_plume_advance(nmf_plume* P, int n_ticks, void* stream) {
+  if (!P) return fail("nmf_plume_advance: null plume");
+  if (n_ticks < 1) return fail("nmf_plume_advance: n_ticks must be at least 1, got " + std::to_string(n_ticks));
+  DEVICE_GUARD(P);
+  const nmf::PlumeArgs& A = P->args;
+  const unsigned tiles = (unsigned)(((A.W + nmf::kPlumeTileW - 1) / nmf::kPlumeTileW) * ((A.H + nmf::kPlumeTileH - 1) / nmf::kPlumeTileH));
+  for (int t = 0; t < n_ticks; ++t) {
+    hipLaunchKernelGGL(nmf::nmf_plume_tick_kernel, dim3(tiles * (unsigned)A.n_plumes), dim3(nmf::kPlumeThreads), 0, (hipStream_t)stream,
+                       A, P->parity, P->wind, P->eddies, P->source, P->grid[0], P->grid[1]);
+    hipLaunchKernelGGL(nmf::nmf_plume_wind_kernel, dim3((unsigned)((A.n_plumes + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       A, P->parity, P->wind, P->ticks);
+  }
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int nmf_plume_sample_points(nmf_plume* P, const float* points_dev, int n_pts, float* out_dev, uint8_t* oob_dev, void* stream) {
+  if (!P) return fail("nmf_plume_sample_points: null plume");
+  if (!points_dev || !out_dev || !oob_dev) return fail("nmf_plume_sample_points: null buffer");
+  if (n_pts < 1) return fail("nmf_plume_sample_points: n_pts must be at least 1, got " + std::to_string(n_pts));
+  DEVICE_GUARD(P);
+  constexpr int per_block = nmf::kPlumeSampleThreads / nmf::kWave;
+  hipLaunchKernelGGL(nmf::nmf_plume_sample_points_kernel, dim3((unsigned)((P->n_worlds + per_block - 1) / per_block)), dim3(nmf::kPlumeSampleThreads),
+                     0, (hipStream_t)stream, P->args, P->n_worlds, P->parity, P->grid[0], P->grid[1], points_dev, n_pts, out_dev, oob_dev);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int nmf_plume_sample_sites(nmf_plume* P, const int32_t* sensor_seg_dev, const float* sensor_rel_dev, int n_sensors, float* out_dev,
+                                      uint8_t* oob_dev, void* stream) {
+  if (!P) return fail("nmf_plume_sample_sites: null plume");
+  if (!sensor_seg_dev || !sensor_rel_dev || !out_dev || !oob_dev) return fail("nmf_plume_sample_sites: null buffer");
+  if (n_sensors < 1) return fail("nmf_plume_sample_sites: n_sensors must be at least 1, got " + std::to_string(n_sensors));
+  DEVICE_GUARD(P);
+  const nmf_batch* b = P->batch;
+  constexpr int per_block = nmf::kPlumeSampleThreads / nmf::kWave;
+  hipLaunchKernelGGL(nmf::nmf_plume_sample_sites_kernel, dim3((unsigned)((P->n_worlds + per_block - 1) / per_block)), dim3(nmf::kPlumeSampleThreads),
+                     0, (hipStream_t)stream, P->args, P->n_worlds, P->parity, P->grid[0], P->grid[1], b->st.seg_xpos, b->st.seg_xquat,
+                     b->model->nseg, sensor_seg_dev, sensor_rel_dev, n_sensors, out_dev, oob_dev);
+  HIP_OK(hipGetLastError());
+  return 0;
 }
 
 extern "C" int nmf_odor_intensity(nmf_batch* b, const int32_t* sensor_seg_dev, const float* sensor_rel_dev, int n_sensors,

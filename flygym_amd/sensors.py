@@ -11,9 +11,11 @@ names (``:199-200``) are not shipped, and no code exists, so the following is *b
 * 30 % of the ommatidia are "pale" (read the blue channel), the rest "yellow" (read green), drawn once with
   ``numpy.random.default_rng(0)``;
 * a reading is the mean of the cell's pixels in its channel / 255, stored in channel 0 (yellow) or 1 (pale);
-* odor intensity = sum over sources of ``peak / distance**2`` at the four sensor sites.
+* odor intensity = sum over sources of ``peak / distance**2`` at the four sensor sites (:class:`OdorSensors`), or the reading
+  of a time-varying plume grid per world, advected by a noisy wind beside the physics (:class:`OdorPlume`; the reference holds
+  no plume code or data: the whole model is stated in include/nmf.h and specified by tests/plume_spec.py).
 
-The arithmetic runs in ``libnmf_hip.so`` (``nmf_retina_resample``, ``nmf_odor_intensity``).
+The arithmetic runs in ``libnmf_hip.so`` (``nmf_retina_resample``, ``nmf_odor_intensity``, ``nmf_plume_*``).
 """
 
 from __future__ import annotations
@@ -24,7 +26,7 @@ import numpy as np
 
 from . import _native
 
-__all__ = ["Retina", "OdorSensors", "RAW_IMG_HEIGHT", "RAW_IMG_WIDTH", "NUM_OMMATIDIA"]
+__all__ = ["Retina", "OdorSensors", "OdorPlume", "RAW_IMG_HEIGHT", "RAW_IMG_WIDTH", "NUM_OMMATIDIA"]
 
 RAW_IMG_HEIGHT = 512     # flygym1_config.yaml:143
 RAW_IMG_WIDTH = 450      # :144
@@ -158,4 +160,192 @@ class OdorSensors:
         _native.check(_native.lib().nmf_odor_intensity(
             self.sim._batch_h, self._seg.data_ptr(), self._rel.data_ptr(), 4, self._pos.data_ptr(),
             self._peak.data_ptr(), len(self.source_positions), self.n_dims, out.data_ptr(), self.sim._stream()))
+        return out
+
+
+class _PlumeParams(ctypes.Structure):
+    """``nmf_plume_params`` of include/nmf.h."""
+
+    _fields_ = [("n_plumes", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("first_world", ctypes.c_int32),
+                ("cell_size", ctypes.c_float), ("origin_x", ctypes.c_float), ("origin_y", ctypes.c_float), ("tick_s", ctypes.c_float),
+                ("diffusivity", ctypes.c_float), ("mean_wind_x", ctypes.c_float), ("mean_wind_y", ctypes.c_float),
+                ("wind_tau", ctypes.c_float), ("wind_sigma", ctypes.c_float), ("eddy_gain", ctypes.c_float),
+                ("intensity_scale", ctypes.c_float), ("seed", ctypes.c_uint32)]
+
+
+class OdorPlume:
+    """Time-varying odor plumes on the GPU, one per world, and the fly's four odor sensors in them (``nmf_plume_*``).
+
+    A plume is a float32 concentration grid over the ground plane (cell ``(j, i)`` centred at ``origin + ((i + 1/2), (j + 1/2)) *
+    cell_size``; outside the grid the concentration is 0).  One :meth:`advance` tick of ``tick_s`` seconds advects it with the
+    plume's wind plus ``eddy_gain * eddies`` (semi-Lagrangian, any displacement), diffuses it (``diffusivity``), holds the source
+    cells at their peak (``max`` with the source map), and then moves the wind one Ornstein-Uhlenbeck step towards ``mean_wind``
+    (``wind_tau``, ``wind_sigma``; counter-based noise from ``seed``, the world's index and the tick).  The model is build-defined
+    (the reference ships no plume): its statement is include/nmf.h, its specification in numpy tests/plume_spec.py.
+
+    Args:
+        sim: the batch; a world with several flies resolves to ``sim.for_fly(fly_name)``.
+        fly_name: the fly whose odor sensor sites :meth:`get_odor_intensities` reads.
+        grid: ``(H, W)`` cells, 8..1024 each.  cell_size, origin: the cell's edge and the grid's corner of least ``(x, y)``.
+        source: ``(x, y, radius, peak)`` — the cells whose centre lies within ``radius`` of ``(x, y)`` are held at ``peak`` — or an
+            explicit ``(H, W)`` source map.
+        mean_wind, wind_tau, wind_sigma: the wind process (``wind_sigma=0``: the wind relaxes to ``mean_wind`` and stays).
+        diffusivity: ``kappa``; ``kappa * tick_s / cell_size**2`` must not exceed 1/4.
+        eddies: optional static ``(H, W, 2)`` velocity field added to every plume's wind, times ``eddy_gain``.
+        intensity_scale: factor of every reading.
+        per_world: one plume per world (default), or one plume that all worlds smell.
+        seed, first_world: the noise stream; plume ``p`` draws as world ``first_world + p`` (the placement of a shard inside a
+            larger population, as ``TurningCPG.reset``).
+
+    ``wind`` ``(n_plumes, 2)`` float32 and ``ticks`` ``(n_plumes,)`` int32 are zero-copy views of the device state, writable between
+    launches; so are ``buffers`` (the two ``(n_plumes, H, W)`` grids, ping and pong) and ``parity`` (one int32 word on the device:
+    the index of the current buffer, which every kernel reads and every tick flips).  Every method is stream-ordered device work on the simulation's stream except :meth:`concentration`, which reads one
+    word back; :meth:`advance` and the readings can be captured in a graph and replayed.
+    """
+
+    def __init__(self, sim, fly_name: str, *, grid, cell_size: float, origin=(0.0, 0.0), source, mean_wind=(0.0, 0.0),
+                 wind_tau: float = 1.0, wind_sigma: float = 0.0, diffusivity: float = 0.0, tick_s: float = 0.01, eddies=None,
+                 eddy_gain: float = 1.0, intensity_scale: float = 1.0, per_world: bool = True, seed: int = 0, first_world: int = 0):
+        from .simulation import _tensor_from_ptr
+
+        if hasattr(sim, "for_fly"):          # a world with several flies: this fly's batch
+            sim = sim.for_fly(fly_name)
+        self.sim, self.fly_name = sim, fly_name
+        fly = sim.world.fly_lookup[fly_name]
+        names = [s.name for s in fly.get_bodysegs_order()]
+        H, W = (int(v) for v in grid)
+        self.grid, self.cell_size, self.origin = (H, W), float(cell_size), (float(origin[0]), float(origin[1]))
+        self.n_worlds, self.tick_s = int(sim.n_worlds), float(tick_s)
+        self.n_plumes = self.n_worlds if per_world else 1
+        src = np.asarray(source, dtype=np.float32)
+        if src.ndim == 1 and src.size == 4:
+            src = self.disc_source((H, W), self.cell_size, self.origin, *(float(v) for v in src))
+        if src.shape != (H, W):
+            raise ValueError(f"source must be (x, y, radius, peak) or a map of shape {(H, W)}, got shape {src.shape}")
+        self.source = np.ascontiguousarray(src, dtype=np.float32)
+        self.eddies = None
+        if eddies is not None:
+            self.eddies = np.ascontiguousarray(eddies, dtype=np.float32)
+            if self.eddies.shape != (H, W, 2):
+                raise ValueError(f"eddies must have shape {(H, W, 2)}, got {self.eddies.shape}")
+        lib = _native.lib()
+        if ctypes.sizeof(_PlumeParams) != lib.nmf_plume_params_size():
+            raise _native.NativeError("nmf_plume_params layout mismatch between sensors.py and libnmf_hip.so")
+        self._params = _PlumeParams(self.n_plumes, H, W, int(first_world), self.cell_size, self.origin[0], self.origin[1], self.tick_s,
+                                    float(diffusivity), float(mean_wind[0]), float(mean_wind[1]), float(wind_tau), float(wind_sigma),
+                                    float(eddy_gain), float(intensity_scale), int(seed) & 0xFFFFFFFF)
+        self._h = lib.nmf_plume_create(sim._batch_h, ctypes.byref(self._params), self.source.ctypes.data,
+                                       None if self.eddies is None else self.eddies.ctypes.data)
+        if not self._h:
+            raise _native.NativeError(lib.nmf_last_error().decode())
+        t = sim._torch
+        dev = sim.device
+
+        def view(which, shape, typestr="<f4"):
+            ptr = lib.nmf_plume_field_ptr(self._h, which, None)
+            if not ptr:
+                raise _native.NativeError(lib.nmf_last_error().decode())
+            return _tensor_from_ptr(t, ptr, shape, dev, typestr)
+
+        self.wind = view(0, (self.n_plumes, 2))
+        self.ticks = view(1, (self.n_plumes,), "<i4")
+        self.buffers = (view(2, (self.n_plumes, H, W)), view(3, (self.n_plumes, H, W)))
+        self.parity = view(4, (1,), "<i4")
+        self._seg = t.as_tensor(np.array([names.index(n) for n, _ in ODOR_SENSOR_SITES], dtype=np.int32), device=dev)
+        self._rel = t.as_tensor(np.array([r for _, r in ODOR_SENSOR_SITES], dtype=np.float32), device=dev)
+        self.out_of_bounds = t.zeros((self.n_worlds,), dtype=t.uint8, device=dev)
+
+    @staticmethod
+    def disc_source(grid, cell_size, origin, x, y, radius, peak) -> np.ndarray:
+        """``(H, W)`` float32 source map: ``peak`` in the cells whose centre lies within ``radius`` of ``(x, y)``, 0 elsewhere."""
+        H, W = grid
+        xc = origin[0] + (np.arange(W, dtype=np.float64) + 0.5) * cell_size
+        yc = origin[1] + (np.arange(H, dtype=np.float64) + 0.5) * cell_size
+        inside = (xc[None, :] - x) ** 2 + (yc[:, None] - y) ** 2 <= radius ** 2
+        return np.where(inside, np.float32(peak), np.float32(0)).astype(np.float32)
+
+    # ---- lifecycle
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _native.lib().nmf_plume_destroy(self._h)
+            self._h = None
+            self.wind = self.ticks = self.buffers = self.parity = None        # (views of freed memory)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _handle(self):
+        if not getattr(self, "_h", None):
+            raise RuntimeError("the plume is closed")
+        return self._h
+
+    # ---- the field
+    def advance(self, n_ticks: int = 1) -> None:
+        """``n_ticks`` plume ticks of every plume (two launches per tick; no host sync)."""
+        _native.check(_native.lib().nmf_plume_advance(self._handle(), int(n_ticks), self.sim._stream()))
+
+    def reset(self, mask=None) -> None:
+        """The plumes of ``mask`` (``(n_plumes,)`` bool, numpy or torch; default all) get empty grids, tick 0 and the mean wind;
+        the others keep their state."""
+        h = self._handle()
+        t = self.sim._torch
+        m = None
+        if mask is not None:
+            m = t.as_tensor(mask, device=self.sim.device)
+            if tuple(m.shape) != (self.n_plumes,):
+                raise ValueError(f"Expected a reset mask of shape ({self.n_plumes},), but got {tuple(m.shape)}")
+            m = (m != 0).to(t.uint8).contiguous()
+        _native.check(_native.lib().nmf_plume_reset(h, None if m is None else m.data_ptr(), self.sim._stream()))
+
+    def set_wind(self, wind) -> None:
+        """``(2,)`` or ``(n_plumes, 2)``, numpy or torch: copied into :attr:`wind` on the simulation's stream."""
+        self._handle()
+        t = self.sim._torch
+        if not isinstance(wind, t.Tensor):
+            wind = t.as_tensor(np.array(wind, dtype=np.float32))
+        if tuple(wind.shape) not in ((2,), (self.n_plumes, 2)):
+            raise ValueError(f"Expected a wind of shape (2,) or ({self.n_plumes}, 2), but got {tuple(wind.shape)}")
+        self.wind.copy_(wind.to(device=self.sim.device, dtype=t.float32).expand(self.n_plumes, 2))
+
+    def concentration(self):
+        """The current grids, ``(n_plumes, H, W)`` float32: a zero-copy view of the buffer the parity word names (read back, so
+        this waits for the stream).  The next tick makes it the OLD buffer: clone it to keep it."""
+        self._handle()
+        return self.buffers[int(self.parity.item()) & 1]
+
+    # ---- the readings
+    def sample(self, points):
+        """Readings at ``points`` ``(n_worlds, n_pts, 2)`` (x, y), numpy or torch -> float32 ``(n_worlds, n_pts)`` on the device;
+        sets :attr:`out_of_bounds`."""
+        h = self._handle()
+        t = self.sim._torch
+        pts = t.as_tensor(points).to(device=self.sim.device, dtype=t.float32).contiguous()
+        if pts.ndim != 3 or pts.shape[0] != self.n_worlds or pts.shape[2] != 2 or pts.shape[1] < 1:
+            raise ValueError(f"Expected points of shape ({self.n_worlds}, n_pts, 2), but got {tuple(pts.shape)}")
+        out = t.empty((self.n_worlds, int(pts.shape[1])), dtype=t.float32, device=self.sim.device)
+        _native.check(_native.lib().nmf_plume_sample_points(h, pts.data_ptr(), int(pts.shape[1]), out.data_ptr(),
+                                                            self.out_of_bounds.data_ptr(), self.sim._stream()))
+        return out
+
+    def get_odor_intensities(self, out=None):
+        """float32 ``(n_worlds, 1, 4)`` at the four odor sensor sites (the layout of :meth:`OdorSensors.get_odor_intensities`
+        with one odor dimension) from the poses of the last step; sets :attr:`out_of_bounds`.  ``out``: a tensor to fill."""
+        h = self._handle()
+        t = self.sim._torch
+        if out is None:
+            out = t.empty((self.n_worlds, 1, 4), dtype=t.float32, device=self.sim.device)
+        elif (tuple(out.shape) != (self.n_worlds, 1, 4) or out.dtype != t.float32 or not out.is_contiguous()
+              or out.device != t.device(self.sim.device)):
+            raise ValueError(f"out must be a contiguous float32 tensor of shape ({self.n_worlds}, 1, 4) on {self.sim.device}")
+        _native.check(_native.lib().nmf_plume_sample_sites(h, self._seg.data_ptr(), self._rel.data_ptr(), 4, out.data_ptr(),
+                                                           self.out_of_bounds.data_ptr(), self.sim._stream()))
         return out

@@ -27,6 +27,7 @@ typedef struct nmf_batch nmf_batch;
 typedef struct nmf_eye_plan nmf_eye_plan;
 typedef struct nmf_camera_plan nmf_camera_plan;
 typedef struct nmf_cpg nmf_cpg;
+typedef struct nmf_plume nmf_plume;
 
 /* Per-world fields addressable through nmf_field_ptr / nmf_gather_* */
 enum nmf_field {
@@ -461,6 +462,95 @@ int nmf_cpg_hybrid_enable(nmf_cpg* cpg, const nmf_cpg_hybrid_params* params, con
  * allocation, no host synchronisation, hipGraph-capturable.  Refused: a controller without nmf_cpg_hybrid_enable, and everything
  * nmf_cpg_advance refuses.  nmf_cpg_reset also zeroes rho / sigma / flags of the masked worlds once the rules are enabled. */
 int nmf_cpg_advance_hybrid(nmf_cpg* cpg, int n_steps, float* table_dev, int table_steps, void* stream);
+
+/* Advected odor plumes with their state on the device (flygym_amd.sensors.OdorPlume; csrc/nmf_plume.hip).  No reference
+ * counterpart: the snapshot holds no plume code and no plume data (flygym 1.x replayed one recording of an offline fluid simulation
+ * to one fly), so the whole model is build-defined and pinned by nothing (specification tests/plume_spec.py).
+ * A plume is a float32 concentration grid c[height][width] over the ground plane: cell (j, i) is centred at
+ * (origin_x + (i + 1/2) cell_size, origin_y + (j + 1/2) cell_size), and cells outside the grid read as 0 everywhere below (clean
+ * air flows in, odor flows out).  A handle holds n_plumes of them — 1 (every world smells the same plume) or the batch's n_worlds —
+ * each with two grids (ping and pong), a wind w = (wx, wy) float32 and a tick counter (uint32); WHICH grid is current is one parity
+ * word in device memory, read by every kernel and flipped by every tick.  One tick of tick_s seconds, every cell from the old grid:
+ *   v = w + eddy_gain E[j][i]                                  (E[height][width][2]: optional static eddies, shared by all plumes)
+ *   d = vx r, k = floor(d), f = d - k; (l, g) likewise from vy (r = tick_s / cell_size: any displacement is legal, no CFL clamp)
+ *   adv = (1 - g) ((1 - f) c[j-l][i-k] + f c[j-l][i-k-1]) + g ((1 - f) c[j-l-1][i-k] + f c[j-l-1][i-k-1])
+ *   dif = D (c[j][i-1] + c[j][i+1] + c[j-1][i] + c[j+1][i] - 4 c[j][i])             (D = diffusivity tick_s / cell_size^2)
+ *   c_new[j][i] = max(adv + dif, S[j][i])                      (S[height][width]: the source map, shared by all plumes)
+ * and then, per plume, one Ornstein-Uhlenbeck step of the wind and tick <- tick + 1:
+ *   w <- (w + a (mean_wind - w)) + b xi        a = tick_s / wind_tau, b = wind_sigma sqrt(tick_s); per component
+ *   xi = ((u0 + u1) + (u2 + u3) - 2) sqrt(3),  u_m = (hash(x_m) >> 8) 2^-24,
+ *   x_m = seed ^ (world 0x9E3779B9) ^ (tick 0x85EBCA6B) ^ (m 0xC2B2AE35)   (uint32; m = 0..3 for x, 4..7 for y; tick: before its increment)
+ *   hash(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ * world = first_world + the plume's index (the placement of a shard inside a larger population, as nmf_cpg_reset's).  r, D, a and
+ * b are computed in float64 and rounded to float32 once; the grid, wind and reading arithmetic is float32 with every operation rounded
+ * as written above (no contraction, no reassociation; the reading's division correctly rounded).  The diffusion term is taken at
+ * the cell, not at its upstream point: a wind within 2 D cells of an odd whole number of cells per tick amplifies cell-to-cell
+ * stripes, and the concentration may exceed the source's peak.  wind_sigma = 0 gives a deterministic wind; the caller may overwrite the wind between
+ * launches (NMF_PLUME_WIND).  Every cell is written by one lane from the old grid alone (no atomics): results are bitwise
+ * reproducible from run to run.
+ * A reading at the point (x, y) is the current grid interpolated bilinearly between cell centres, times intensity_scale:
+ *   u = (x - origin_x) / cell_size - 1/2, i0 = floor(u), f = u - i0; (v, j0, g) likewise from y
+ *   reading = intensity_scale ((1 - g) ((1 - f) c[j0][i0] + f c[j0][i0+1]) + g ((1 - f) c[j0+1][i0] + f c[j0+1][i0+1]))
+ * so it falls to 0 continuously at the border; a point with u outside [-1/2, width - 1/2] or v outside [-1/2, height - 1/2] (or
+ * not a number) sets its world's out-of-bounds byte. */
+typedef struct nmf_plume_params {
+  int32_t n_plumes;             /* 1, or the batch's n_worlds                                                            */
+  int32_t height, width;        /* cells (8..1024 each)                                                                  */
+  int32_t first_world;          /* global index of plume 0 in the noise's world term (>= 0)                              */
+  float cell_size;              /* h, in the model's length unit (> 0)                                                   */
+  float origin_x, origin_y;     /* the grid's corner of least x and y                                                    */
+  float tick_s;                 /* seconds per plume tick (> 0)                                                          */
+  float diffusivity;            /* kappa, length^2 per second (>= 0; kappa tick_s / h^2 <= 1/4)                          */
+  float mean_wind_x, mean_wind_y;   /* length per second                                                                 */
+  float wind_tau;               /* relaxation time of the wind, seconds (> 0)                                            */
+  float wind_sigma;             /* noise amplitude of the wind, length per second per sqrt(second) (>= 0)                */
+  float eddy_gain;              /* scale of the eddy field (ignored without one)                                         */
+  float intensity_scale;        /* factor of every reading                                                               */
+  uint32_t seed;
+} nmf_plume_params;
+
+/* sizeof(nmf_plume_params) as this library was compiled (as nmf_eye_params_size). */
+size_t nmf_plume_params_size(void);
+
+/* An explicit handle for the worlds of `batch`, on its device: takes HOST arrays — source[height][width] float32 and
+ * eddies[height][width][2] float32 or NULL — validates them, owns device copies and the state arrays, and resets every plume
+ * (nmf_plume_reset with a NULL mask; parity 0).  NOT stream-ordered (allocations, synchronous uploads); must not be called inside
+ * a stream capture.  NULL on error (nmf_last_error): n_plumes other than 1 or the batch's n_worlds; height or width outside
+ * 8..1024; kappa tick_s / h^2 > 1/4; a cell_size, tick_s or wind_tau that is not positive; a negative diffusivity, wind_sigma or
+ * first_world; a value that is not finite in the params, the source map or the eddies; a NULL source map.  The handle keeps
+ * pointers to the batch's seg_xpos / seg_xquat arrays (nmf_plume_sample_sites): destroy it before the batch. */
+nmf_plume* nmf_plume_create(nmf_batch* batch, const nmf_plume_params* params, const float* source, const float* eddies);
+void nmf_plume_destroy(nmf_plume* plume);
+
+/* The plumes with mask_dev[p] != 0 (uint8 per PLUME, device memory; NULL: all) get both grids zeroed, tick = 0 and w = mean_wind;
+ * the others are not touched, and neither is the parity word.  Stream-ordered. */
+int nmf_plume_reset(nmf_plume* plume, const uint8_t* mask_dev, void* stream);
+
+/* n_ticks ticks of every plume: argument checks and, per tick, two kernel launches on `stream` (the grids, then winds / tick
+ * counters / parity).  No allocation, no host synchronisation, hipGraph-capturable: the kernels find the current grid through the
+ * parity word, so a captured advance replays correctly any number of times.  Refused: n_ticks < 1. */
+int nmf_plume_advance(nmf_plume* plume, int n_ticks, void* stream);
+
+/* Device pointer + row width of an array of the handle (zero-copy views; writable between launches). */
+#define NMF_PLUME_WIND 0          /* [n_plumes][2] float32                                                        */
+#define NMF_PLUME_TICKS 1         /* [n_plumes][1] uint32                                                         */
+#define NMF_PLUME_GRID0 2         /* [n_plumes][height * width] float32: the current grids while the parity is 0  */
+#define NMF_PLUME_GRID1 3         /* [n_plumes][height * width] float32: the current grids while the parity is 1  */
+#define NMF_PLUME_PARITY 4        /* ONE int32 word, 0 or 1 (width 1; not per plume)                              */
+void* nmf_plume_field_ptr(nmf_plume* plume, int which, int32_t* width);
+
+/* Readings at caller-given points: points_dev[n_worlds][n_pts][2] float32 (x, y) -> out_dev[n_worlds][n_pts] float32, and
+ * oob_dev[n_worlds] uint8 = 1 where any of the world's points lies out of bounds (else 0).  World w reads plume w (plume 0 when
+ * n_plumes is 1).  Argument checks and ONE kernel launch on `stream`: no allocation, no host synchronisation, capturable.
+ * Refused: a null buffer, n_pts < 1. */
+int nmf_plume_sample_points(nmf_plume* plume, const float* points_dev, int n_pts, float* out_dev, uint8_t* oob_dev, void* stream);
+
+/* Readings at n_sensors points rigidly attached to segments, placed exactly as nmf_odor_intensity places them (sensor_seg = index
+ * into the batch's segment order, clamped to it; sensor_rel = offset in the segment frame; the point is the x, y of seg_xpos +
+ * R(seg_xquat) rel, z is ignored): out_dev[n_worlds][n_sensors] float32 and oob_dev[n_worlds] uint8 as above, from the poses of the
+ * last nmf_step / nmf_reset.  ONE kernel launch on `stream`, capturable.  Refused: a null buffer, n_sensors < 1. */
+int nmf_plume_sample_sites(nmf_plume* plume, const int32_t* sensor_seg_dev, const float* sensor_rel_dev, int n_sensors,
+                           float* out_dev, uint8_t* oob_dev, void* stream);
 
 /* Odor intensity at n_sensors points rigidly attached to named segments (sensor_seg = index into the
  * batch's segment order, sensor_rel = offset in the segment frame): out[w][d][k] = sum_s peak[s][d] / dist^2.
