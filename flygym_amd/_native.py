@@ -182,6 +182,8 @@ def lib():
             "nmf_plume_field_ptr": (vp, [vp, ci, ctypes.POINTER(ctypes.c_int32)]),
             "nmf_plume_sample_points": (ci, [vp, vp, ci, vp, vp, vp]),
             "nmf_plume_sample_sites": (ci, [vp, vp, vp, ci, vp, vp, vp]),
+            "nmf_taxis_params_size": (ctypes.c_size_t, []),
+            "nmf_taxis_update": (ci, [vp, vp, ci, ci, ci, vp, vp, vp, ci, ci, vp, vp, vp, vp]),
             "nmf_odor_intensity": (ci, [vp, vp, vp, ci, vp, vp, ci, ci, vp, vp]),
             "nmf_replay_resample": (ci, [vp, ci, ci, ctypes.c_double, ctypes.c_double, vp, ci, ci, vp, vp]),
         }

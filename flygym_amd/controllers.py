@@ -31,6 +31,10 @@ build-defined and pinned by nothing: the rules are this project's statement of t
 remembered): a leg that hangs much lower than the others (it stepped into a gap) and a leg that is pushed backwards
 while it swings (it hit a wall) are lifted by a correction added to their targets.  The rules read the batch's pose and contact
 sensors once per launch; the oscillators are not changed by them.
+
+``SensorySteering`` closes the loop from the senses: one stateless launch (``csrc/nmf_taxis.hip``; specification
+``tests/taxis_spec.py``) turns the ommatidia readings of both eyes and the readings of the four odor sites into the drive of a
+``TurningCPG`` — flygym 1.x's visual taxis and odor taxis, build-defined and pinned by nothing.
 """
 
 from __future__ import annotations
@@ -44,7 +48,7 @@ from .anatomy import LEGS, JointDOF
 from .replay import MotionSnippet
 from .simulation import _field_view
 
-__all__ = ["TripodCPG", "TurningCPG", "HybridTurningCPG"]
+__all__ = ["TripodCPG", "TurningCPG", "HybridTurningCPG", "SensorySteering"]
 
 TRIPOD_PHASE_BIAS = {"lf": 0.0, "rm": 0.0, "lh": 0.0, "rf": np.pi, "lm": np.pi, "rh": np.pi}
 
@@ -433,3 +437,122 @@ class HybridTurningCPG(TurningCPG):
     def close(self) -> None:
         super().close()
         self.retraction = self.stumbling = self.rule_flags = None
+
+
+class _TaxisParams(ctypes.Structure):
+    """``nmf_taxis_params`` of include/nmf.h."""
+
+    _fields_ = [("obj_threshold", ctypes.c_float), ("area_threshold", ctypes.c_float), ("visual_gain", ctypes.c_float),
+                ("v_min", ctypes.c_float), ("v_max", ctypes.c_float), ("w_ant", ctypes.c_float), ("w_palp", ctypes.c_float),
+                ("odor_delta", ctypes.c_float), ("base", ctypes.c_float), ("drive_min", ctypes.c_float), ("drive_max", ctypes.c_float),
+                ("front_edge", ctypes.c_int32 * 2)]
+
+
+def eye_front_edges() -> tuple:
+    """Per eye of ``sensors.EYE_CAMERAS``: 1 when the fly's forward axis (+x of the eye's parent frame) has a positive component
+    along the camera's right axis — column 0 of the camera matrix ``Rz Ry Rx`` of the eye's Euler triple — so that the image's
+    LAST column faces forward; 0 when column 0 does.  (1, 0): left eye +0.892, right eye -0.892."""
+    from .sensors import EYE_CAMERAS
+
+    out = []
+    for _, (_, e) in EYE_CAMERAS.items():
+        # (Rz Ry Rx)[0, 0] = cos(e2) cos(e1)
+        out.append(int(np.cos(e[2]) * np.cos(e[1]) > 0))
+    return tuple(out)
+
+
+class SensorySteering:
+    """Eyes and antennae steer the CPG: one launch per control tick turns the ommatidia readings of both eyes
+    (``EyeRenderer.render_into``) and the readings of the four odor sites (``OdorSensors`` / ``OdorPlume.get_odor_intensities``)
+    into the drive ``(left, right)`` of a :class:`TurningCPG` (``nmf_taxis_update``, ``csrc/nmf_taxis.hip``; the model is stated in
+    include/nmf.h and specified by tests/taxis_spec.py).  Stateless: no handle, nothing to close.
+
+    Visual taxis (follow a dark object): an ommatidium is dark when its reading is below ``obj_threshold``; per eye ``area`` is the
+    dark share of the ommatidia and ``(cx, cy)`` the mean centre of the dark ones in units of the image's width and height.  An eye
+    has found the object when ``area > area_threshold``; its side's speed is then ``clip(1 - visual_gain * dev, v_min, v_max)``, ``dev``
+    being the object's normalised distance from the image edge that faces forward (:attr:`front_edge`) — so the fly slows the
+    side a lateral object is on and turns towards it — and 1 otherwise.
+
+    Odor taxis: per odor dimension ``d`` the left and right readings are ``w_ant * antenna + w_palp * palp``, their contrast is
+    ``c_d = (L - R) / (L + R)`` (0 without odor), ``b = sum_d odor_gains[d] * c_d`` (a positive gain attracts, a negative one
+    repels), ``q = b |b| / (1 + b^2)``; the left speed is scaled by ``1 - odor_delta * max(q, 0)``, the right one by
+    ``1 - odor_delta * max(-q, 0)``.
+
+    ``drive[side] = clip(base * v_side * o_side, drive_min, drive_max)``, side 0 = left: the order of ``TurningCPG.drive``.  The
+    defaults are flygym 1.x's constants as remembered (its source is not at hand); build-defined and pinned by nothing.
+
+    Args:
+        sim: the batch; a world with several flies resolves to ``sim.for_fly(fly_name)``.
+        fly_name: the fly that is steered.
+        retina: the retina whose readings :meth:`update` takes (default: the default :class:`~flygym_amd.sensors.Retina`); at most
+            2047 pixels a side and 1024 ommatidia.
+        odor_gains: one gain per odor dimension (at most 8).
+
+    ``features`` ``(n, 2, 3)`` (cy, cx, area per eye), ``bias`` ``(n,)`` (the value ``b``) and ``drive`` ``(n, 2)`` are float32
+    tensors allocated once and overwritten by every :meth:`update`.
+    """
+
+    def __init__(self, sim, fly_name: str, *, retina=None, odor_gains=(), obj_threshold: float = 0.15, area_threshold: float = 0.01,
+                 visual_gain: float = 3.0, v_min: float = 0.4, v_max: float = 1.2, w_ant: float = 10.0 / 11.0, w_palp: float = 1.0 / 11.0,
+                 odor_delta: float = 0.8, base: float = 1.0, drive_min: float = 0.2, drive_max: float = 1.2):
+        from .sensors import Retina
+
+        if hasattr(sim, "for_fly"):          # a world with several flies: this fly's batch
+            sim = sim.for_fly(fly_name)
+        if fly_name not in sim.world.fly_lookup:
+            raise ValueError(f"no fly named {fly_name!r} in this simulation ({', '.join(sim.world.fly_lookup)})")
+        self.sim, self.fly_name = sim, fly_name
+        self.retina = retina or Retina()
+        self.n_worlds, self.n_omm = int(sim.n_worlds), int(self.retina.num_ommatidia)
+        table = self.retina.centre_table()                       # (refuses a retina the kernel's table cannot hold)
+        self.odor_gains = tuple(float(g) for g in odor_gains)
+        self.n_dims = len(self.odor_gains)
+        if self.n_dims > 8:
+            raise ValueError(f"at most 8 odor dimensions, got {self.n_dims} gains")
+        self.front_edge = eye_front_edges()
+        lib = _native.lib()
+        if ctypes.sizeof(_TaxisParams) != lib.nmf_taxis_params_size():
+            raise _native.NativeError("nmf_taxis_params layout mismatch between controllers.py and libnmf_hip.so")
+        self._params = _TaxisParams(float(obj_threshold), float(area_threshold), float(visual_gain), float(v_min), float(v_max),
+                                    float(w_ant), float(w_palp), float(odor_delta), float(base), float(drive_min), float(drive_max),
+                                    (ctypes.c_int32 * 2)(*self.front_edge))
+        t, dev = sim._torch, sim.device
+        self.centres = t.as_tensor(table, device=dev)            # int16 (n_omm, 2), sixteenths of a pixel
+        # (one element more than the gains: never empty, so its address also stands in for an odor input of no dimensions)
+        self._gains = t.zeros((self.n_dims + 1,), dtype=t.float32, device=dev)
+        if self.n_dims:
+            self._gains[:self.n_dims] = t.as_tensor(np.array(self.odor_gains, dtype=np.float32), device=dev)
+        self.features = t.zeros((self.n_worlds, 2, 3), dtype=t.float32, device=dev)
+        self.bias = t.zeros((self.n_worlds,), dtype=t.float32, device=dev)
+        self.drive = t.ones((self.n_worlds, 2), dtype=t.float32, device=dev)
+
+    def _checked(self, name, x, shape):
+        t = self.sim._torch
+        if (not isinstance(x, t.Tensor) or tuple(x.shape) != shape or x.dtype != t.float32 or x.device != self.sim.device
+                or not x.is_contiguous()):
+            got = f"{tuple(x.shape)} {x.dtype} on {x.device}" if isinstance(x, t.Tensor) else type(x).__name__
+            raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape} on {self.sim.device}, got {got}")
+        return x
+
+    def update(self, omm=None, odor=None, out=None):
+        """One steering update from ``omm`` ``(n_worlds, 2, num_ommatidia, 2)`` and / or ``odor`` ``(n_worlds, n_dims, 4)`` (float32,
+        contiguous, on the simulation's device): one kernel launch on the current stream, no allocation — capturable.  Writes
+        :attr:`features` and :attr:`bias`, and the drive into ``out`` ``(n_worlds, 2)`` (for example ``cpg.drive``) or into
+        :attr:`drive`; returns the drive tensor.  An absent input leaves its factor at 1."""
+        n = self.n_worlds
+        if omm is None and odor is None:
+            raise ValueError("update needs omm, odor or both")
+        if omm is not None:
+            self._checked("omm", omm, (n, 2, self.n_omm, 2))
+        odor_ptr = None
+        if odor is not None:
+            if isinstance(odor, self.sim._torch.Tensor) and odor.ndim == 3 and int(odor.shape[1]) != self.n_dims:
+                raise ValueError(f"odor has {int(odor.shape[1])} dimensions for {self.n_dims} odor_gains")
+            self._checked("odor", odor, (n, self.n_dims, 4))
+            odor_ptr = odor.data_ptr() if self.n_dims else self._gains.data_ptr()
+        drive = self.drive if out is None else self._checked("out", out, (n, 2))
+        _native.check(_native.lib().nmf_taxis_update(
+            ctypes.byref(self._params), self.centres.data_ptr(), self.n_omm, self.retina.height, self.retina.width,
+            None if omm is None else omm.data_ptr(), odor_ptr, self._gains.data_ptr(), self.n_dims, n,
+            self.features.data_ptr(), self.bias.data_ptr(), drive.data_ptr(), self.sim._stream()))
+        return drive

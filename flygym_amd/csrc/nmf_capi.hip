@@ -20,13 +20,15 @@
 #include "nmf_step.hip"
 #include "nmf_sensors.hip"
 // `#pragma clang fp reassociate(off)` at file scope holds from the first file that sets it to the end of the translation unit:
-// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip, nmf_plume.hip and the host code below are all
-// compiled under it, and the files above are not.  Which files it covers decides their kernels' arithmetic: keep the order.
+// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip, nmf_plume.hip, nmf_taxis.hip and the host code
+// below are all compiled under it, and the files above are not.  Which files it covers decides their kernels' arithmetic: keep the
+// order (nmf_taxis.hip adds pragmas inside its functions only: nothing of it reaches past the file).
 #include "nmf_eyes.hip"
 #include "nmf_camera.hip"
 #include "nmf_replay.hip"
 #include "nmf_cpg.hip"
 #include "nmf_plume.hip"
+#include "nmf_taxis.hip"
 #include "nmf_skeleton.h"      // nmf_model, the blob parser, classify_skeleton
 #endif
 
@@ -1508,6 +1510,39 @@ extern "C" int nmf_plume_sample_sites(nmf_plume* P, const int32_t* sensor_seg_de
   hipLaunchKernelGGL(nmf::nmf_plume_sample_sites_kernel, dim3((unsigned)((P->n_worlds + per_block - 1) / per_block)), dim3(nmf::kPlumeSampleThreads),
                      0, (hipStream_t)stream, P->args, P->n_worlds, P->parity, P->grid[0], P->grid[1], b->st.seg_xpos, b->st.seg_xquat,
                      b->model->nseg, sensor_seg_dev, sensor_rel_dev, n_sensors, out_dev, oob_dev);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// ---- sensory steering (nmf_taxis.hip) ----
+extern "C" size_t nmf_taxis_params_size(void) { return sizeof(nmf_taxis_params); }
+
+extern "C" int nmf_taxis_update(const nmf_taxis_params* p, const int16_t* centres_dev, int n_omm, int height, int width, const float* omm_dev,
+                                const float* odor_dev, const float* odor_gains_dev, int n_dims, int n_worlds, float* features_dev,
+                                float* bias_dev, float* drive_dev, void* stream) {
+  if (!p) return fail("nmf_taxis_update: null params");
+  if (!drive_dev) return fail("nmf_taxis_update: null drive");
+  if (!omm_dev && !odor_dev) return fail("nmf_taxis_update: omm and odor are both null (nothing to steer by)");
+  if (n_worlds < 1) return fail("nmf_taxis_update: n_worlds must be at least 1, got " + std::to_string(n_worlds));
+  if (n_dims < 0 || n_dims > nmf::kTaxisMaxDims) return fail("nmf_taxis_update: n_dims must be in 0..8, got " + std::to_string(n_dims));
+  if (omm_dev) {
+    if (n_omm < 1 || n_omm > nmf::kMaxOmmatidia) return fail("nmf_taxis_update: n_omm must be in 1..1024, got " + std::to_string(n_omm));
+    if (height < 1 || height > nmf::kTaxisMaxSide || width < 1 || width > nmf::kTaxisMaxSide)
+      return fail("nmf_taxis_update: need 1 <= height, width <= 2047 pixels, got " + std::to_string(height) + " x " + std::to_string(width));
+    if (!centres_dev) return fail("nmf_taxis_update: null centres");
+    if (((uintptr_t)centres_dev & 3) || ((uintptr_t)omm_dev & 7)) return fail("nmf_taxis_update: centres must be 4-byte and omm 8-byte aligned");
+  }
+  if (odor_dev) {
+    if (n_dims > 0 && !odor_gains_dev) return fail("nmf_taxis_update: null odor gains");
+    if ((uintptr_t)odor_dev & 15) return fail("nmf_taxis_update: odor must be 16-byte aligned");
+  }
+  nmf::TaxisArgs A;
+  A.p = *p;
+  A.n_worlds = n_worlds; A.n_omm = n_omm; A.n_dims = n_dims; A.H = height; A.W = width;
+  constexpr int per_block = nmf::kTaxisThreads / nmf::kWave;
+  hipLaunchKernelGGL(nmf::nmf_taxis_kernel, dim3((unsigned)((n_worlds + per_block - 1) / per_block)), dim3(nmf::kTaxisThreads), 0, (hipStream_t)stream,
+                     A, reinterpret_cast<const int*>(centres_dev), reinterpret_cast<const float2*>(omm_dev), odor_dev, odor_gains_dev,
+                     features_dev, bias_dev, drive_dev);
   HIP_OK(hipGetLastError());
   return 0;
 }

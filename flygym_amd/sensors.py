@@ -36,6 +36,8 @@ EYE_CAMERAS = {          # :164-173  (parent segment, offset mm, euler orientati
     "l_eye": ((-0.03, 0.38, 0.0), (1.57, 0.00, -0.47)),
     "r_eye": ((-0.03, -0.38, 0.0), (-1.57, 3.14, 0.47)),
 }
+MAX_STEERING_SIDE = 2047          # csrc/nmf_taxis.hip: ommatidium centres are int16 sixteenths of a pixel ...
+MAX_STEERING_OMMATIDIA = 1024     # ... and at most kMaxOmmatidia of them are summed
 ODOR_SENSOR_SITES = [    # :175-192  (parent segment, offset in the segment frame, mm)
     ("c_rostrum", (-0.15, 0.15, -0.15)),     # left maxillary palp
     ("c_rostrum", (-0.15, -0.15, -0.15)),    # right maxillary palp
@@ -125,6 +127,25 @@ class Retina:
             inv_norm.data_ptr(), n,
             self.height * self.width, self.num_ommatidia, out.data_ptr(), stream))
         return out
+
+    def ommatidia_centres(self) -> np.ndarray:
+        """float64 ``(num_ommatidia, 2)``: the mean ``(x, y)`` of the pixel centres ``(col + 1/2, row + 1/2)`` of each
+        ommatidium's cell in :attr:`id_map`."""
+        ids = self.id_map.ravel().astype(np.int64)
+        rows, cols = np.divmod(np.arange(ids.size), self.width)
+        counts = self.num_pixels_per_ommatidium.astype(np.float64)
+        x = np.bincount(ids, weights=cols + 0.5, minlength=self.num_ommatidia + 1)[1:] / counts
+        y = np.bincount(ids, weights=rows + 0.5, minlength=self.num_ommatidia + 1)[1:] / counts
+        return np.stack([x, y], axis=-1)
+
+    def centre_table(self) -> np.ndarray:
+        """int16 ``(num_ommatidia, 2)``: :meth:`ommatidia_centres` in sixteenths of a pixel, ``rint(16 * centre)`` — the table
+        the steering kernel sums (``controllers.SensorySteering``).  Refuses a retina that does not fit it."""
+        if max(self.height, self.width) > MAX_STEERING_SIDE:
+            raise ValueError(f"a retina of {self.height} x {self.width} pixels exceeds {MAX_STEERING_SIDE} a side (int16 sixteenths of a pixel)")
+        if self.num_ommatidia > MAX_STEERING_OMMATIDIA:
+            raise ValueError(f"a retina of {self.num_ommatidia} ommatidia exceeds the steering kernel's {MAX_STEERING_OMMATIDIA}")
+        return np.rint(16.0 * self.ommatidia_centres()).astype(np.int16)
 
     def hex_pxls_to_human_readable(self, readings: np.ndarray) -> np.ndarray:
         """Paint ``(num_ommatidia, 2)`` readings back onto the pixel grid (for inspection)."""

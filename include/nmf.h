@@ -552,6 +552,50 @@ int nmf_plume_sample_points(nmf_plume* plume, const float* points_dev, int n_pts
 int nmf_plume_sample_sites(nmf_plume* plume, const int32_t* sensor_seg_dev, const float* sensor_rel_dev, int n_sensors,
                            float* out_dev, uint8_t* oob_dev, void* stream);
 
+/* Sensory steering (flygym_amd.controllers.SensorySteering; csrc/nmf_taxis.hip): the ommatidia readings of both eyes and the
+ * readings of the four odor sites become the CPG's drive (left, right) in ONE launch, with no state and no handle.  No reference
+ * counterpart (the snapshot holds no controller and no vision processing): build-defined and pinned by nothing (DESIGN.md section 7,
+ * specification tests/taxis_spec.py).  Per world:
+ *   per eye e (0 left, 1 right), over the ommatidia i of omm[w][e][i][2]:
+ *     dark_i = omm[i][0] + omm[i][1] < obj_threshold        (strict; one channel is always 0, so the sum is the reading)
+ *     cnt = #dark, Sx = sum_dark qx_i, Sy = sum_dark qy_i   (int32; (qx_i, qy_i) = centres[i]: int16 sixteenths of a pixel)
+ *     cy = Sy / (16 cnt height), cx = Sx / (16 cnt width), area = cnt / n_omm;  (1/2, 1/2, 0) when cnt = 0
+ *       (each quotient: the correctly rounded float64 division of the exact integers, rounded once to float32)
+ *     dev = front_edge[e] ? 1 - cx : cx                      (the object's distance from the image edge that faces forward)
+ *     v_e = area > area_threshold ? min(max(1 - visual_gain dev, v_min), v_max) : 1
+ *   over the odor dimensions d of odor[w][d][4] (sites: palp left, palp right, antenna left, antenna right):
+ *     L_d = w_ant I[d][2] + w_palp I[d][0], R_d = w_ant I[d][3] + w_palp I[d][1], s_d = L_d + R_d
+ *     c_d = s_d > 0 ? (L_d - R_d) / s_d : 0                 (correctly rounded)
+ *   b = sum_d gains[d] c_d (ascending d, from 0);  q = (b |b|) / (1 + b b) (correctly rounded)
+ *   o_0 = 1 - odor_delta max(q, 0), o_1 = 1 - odor_delta max(-q, 0)
+ *   drive[side] = min(max((base v_side) o_side, drive_min), drive_max)          (side 0 = left: the order of NMF_CPG_DRIVE)
+ * Everything after the features is float32 with every operation rounded as written (no contraction, no reassociation), so the
+ * outputs equal the specification's bit for bit whatever the order of the integer reduction.  Without omm, v = 1 and the
+ * features are (1/2, 1/2, 0); without odor, b = 0 and o = 1. */
+typedef struct nmf_taxis_params {
+  float obj_threshold;          /* a reading below this is dark                                                          */
+  float area_threshold;         /* an eye has found an object when more than this share of its ommatidia is dark         */
+  float visual_gain, v_min, v_max;
+  float w_ant, w_palp;          /* weights of the antenna and the palp of a side                                         */
+  float odor_delta;
+  float base, drive_min, drive_max;
+  int32_t front_edge[2];        /* per eye: 1 when the image's LAST column faces forward, 0 when column 0 does           */
+} nmf_taxis_params;
+
+/* sizeof(nmf_taxis_params) as this library was compiled (as nmf_eye_params_size). */
+size_t nmf_taxis_params_size(void);
+
+/* One steering update of n_worlds worlds.  Device buffers: centres_dev[n_omm][2] int16 (4-byte aligned), omm_dev
+ * [n_worlds][2][n_omm][2] float32 (8-byte aligned) or NULL, odor_dev[n_worlds][n_dims][4] float32 (16-byte aligned) or NULL,
+ * odor_gains_dev[n_dims] float32; outputs features_dev[n_worlds][2][3] float32 (cy, cx, area per eye) or NULL, bias_dev[n_worlds]
+ * float32 (b) or NULL, drive_dev[n_worlds][2] float32.  `params` is host memory, read during the call.  Argument checks and ONE
+ * kernel launch on `stream` (of the calling thread's current device): no allocation, no host synchronisation, hipGraph-capturable.
+ * Refused (nmf_last_error): null params or drive; omm and odor both null; n_worlds < 1; n_dims outside 0..8; with omm: n_omm
+ * outside 1..1024, height or width outside 1..2047, null centres; with odor and n_dims > 0: null gains; a misaligned buffer. */
+int nmf_taxis_update(const nmf_taxis_params* params, const int16_t* centres_dev, int n_omm, int height, int width,
+                     const float* omm_dev, const float* odor_dev, const float* odor_gains_dev, int n_dims, int n_worlds,
+                     float* features_dev, float* bias_dev, float* drive_dev, void* stream);
+
 /* Odor intensity at n_sensors points rigidly attached to named segments (sensor_seg = index into the
  * batch's segment order, sensor_rel = offset in the segment frame): out[w][d][k] = sum_s peak[s][d] / dist^2.
  * Reads the pose outputs of the last nmf_step / nmf_reset. */
