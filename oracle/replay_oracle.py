@@ -6,8 +6,9 @@ checked against it — and it against the reference's scipy pipeline (``src/flyg
 import numpy as np
 
 
-def resample(clip: np.ndarray, fps: float, out_dt: float, taps: np.ndarray, window: int) -> np.ndarray:
-    """clip (n_frames, n_cols) -> float32 (n_out, n_cols)."""
+def resample(clip: np.ndarray, fps: float, out_dt: float, taps: np.ndarray, window: int, n_out: int | None = None) -> np.ndarray:
+    """clip (n_frames, n_cols) -> float32 (n_out, n_cols).  ``n_out``: the number of output rows ``k * out_dt`` (the ABI takes
+    any); default the reference's grid ``arange(0, n_frames / fps, out_dt)``, whose values are the same products."""
     x = np.asarray(clip, dtype=np.float32).astype(np.float64)
     n, half = x.shape[0], window // 2
     y = np.zeros_like(x)
@@ -42,7 +43,7 @@ def resample(clip: np.ndarray, fps: float, out_dt: float, taps: np.ndarray, wind
         M[i] -= cp[i] * M[i + 1]
     M[0] = 2.0 * M[1] - M[2]
     M[n - 1] = 2.0 * M[n - 2] - M[n - 3]
-    t = np.arange(0, n / fps, out_dt)
+    t = np.arange(0, n / fps, out_dt) if n_out is None else np.arange(n_out, dtype=np.float64) * out_dt
     x_last = (n - 1) / fps
     i = np.minimum((t * fps).astype(np.int64), n - 2)
     for _ in range(2):
