@@ -286,7 +286,7 @@ nmf_eye_kernel(EyeArgs A, const float* __restrict__ seg_xpos, const float* __res
         float tc = fmaxf(0.f, (A.ground_z + A.terrain[4] - cam.z) * rdz);
 #pragma unroll 1
         for (int it = 0; it < kMaxTerrainCells; ++it) {
-          const float tp = tc + kTerrainEps;
+          const float tp = tc + fmaxf(kTerrainEps, tc * kTerrainEpsRel);      // (relative beyond 210 mm: t + 1e-4 == t in float32 from 1000 mm on, and the walk stood still)
           const TerrainCell c = relief_cell(A.terrain_kind, A.terrain, cam.x + tp * d.x, cam.y + tp * d.y);
           const float h = c.h + A.ground_z;
           const float z_in = cam.z + tc * d.z;

@@ -29,6 +29,7 @@ namespace nmf {
 constexpr int kMaxSpheres = 8;
 constexpr int kMaxTerrainCells = 64;    // cells a ray is followed through the relief before the far field is taken as flat
 constexpr float kTerrainEps = 1e-4f;    // the cell a ray is in at parameter t holds its point at t + eps (mm)
+constexpr float kTerrainEpsRel = 4.76837158203125e-7f;   // ... and eps is no less than t * 2^-21: beyond t = 210 mm a float32 t + 1e-4 stops moving (the eye renderer)
 constexpr float kTerrainWallTol = 1e-4f;   // entered through the side wall: this far below the cell's level (levels differ by >= 0.3 mm)
 
 // constant-height cell of h(x, y) that holds (x, y): bounds (+-inf where unbounded) and level — the same arithmetic as

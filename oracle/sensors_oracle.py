@@ -94,13 +94,15 @@ def euler_xyz_extrinsic_to_mat(e):
 
 MAX_TERRAIN_CELLS = 64       # cells a ray is followed through the relief before the far field is taken as flat
 TERRAIN_EPS = 1e-4           # the cell a ray is in at parameter t is the one that holds its point at t + eps (mm)
+TERRAIN_EPS_REL = 2.0 ** -21  # ... eps being no less than t * 2^-21: in float32 t + 1e-4 == t beyond t = 1000 mm, and a ray that far stood still
 TERRAIN_WALL_TOL = 1e-4      # a cell is entered through its side wall if the ray is this far below its level (levels differ by >= 0.3 mm)
 
 
-def terrain_cell(kind, p, x, y):
+def terrain_cell(kind, p, x, y, dtype=np.float32):
     """(x0, x1, y0, y1, h) of the constant-height cell of the build-defined terrains (flygym_amd/compose/world.py,
-    the same h(x, y) the physics collides with) that holds (x, y); float32, vectorised.  Unbounded sides are +-inf."""
-    f = np.float32
+    the same h(x, y) the physics collides with) that holds (x, y); in ``dtype`` (float32, or float64 for the reference
+    flavour), vectorised.  Unbounded sides are +-inf."""
+    f = dtype
     x, y = np.asarray(x, dtype=f), np.asarray(y, dtype=f)
     inf = np.full(x.shape, np.inf, dtype=f)
 
@@ -138,9 +140,9 @@ def terrain_cell(kind, p, x, y):
     return -inf, inf, -inf, inf, np.zeros(x.shape, dtype=f)
 
 
-def _ray_capsule(d, pa, pb, r):
+def _ray_capsule(d, pa, pb, r, dtype=np.float32):
     """Nearest positive hit parameter of unit rays d (.., 3) from the origin with the capsule (pa, pb, r); inf = miss."""
-    f = np.float32
+    f = dtype
     pa, pb = np.asarray(pa, dtype=f), np.asarray(pb, dtype=f)
     ba = (pb - pa).astype(f)
     baba, baoa, oaoa = f(ba @ ba), f(-(ba @ pa)), f(pa @ pa)
@@ -167,15 +169,21 @@ def _ray_capsule(d, pa, pb, r):
 
 
 def render_eye_frames(cam_pos, cam_mat, height, width, fov_deg, checker_size, ground_z, sky_rgb, ground_rgb,
-                      spheres=(), sphere_rgb=(), terrain=None, wall_rgb=(51, 51, 51), capsules=(), body_rgb=(120, 90, 60)):
+                      spheres=(), sphere_rgb=(), terrain=None, wall_rgb=(51, 51, 51), capsules=(), body_rgb=(120, 90, 60),
+                      dtype=np.float32, return_materials=False):
     """Raw eye frame (height, width, 3) uint8 of one camera — the specification of csrc/nmf_eyes.hip.
+
+    ``dtype``: the arithmetic of every step.  float32 (default) mirrors the kernel's number format; float64 is the reference
+    flavour the parity tests hold the kernel to (tests/test_eye_parity_gpu.py) — the same statements, no shared rounding.
+    ``return_materials``: also return the (height, width) int64 material image: -1 black, 0 sky, 1 / 2 ground checker,
+    3 terrain side wall, 4 own body, 5 + s sphere s.
 
     Camera frame: x right, y up, looking along -z; ``cam_mat`` columns are those axes in world coordinates.
     Equidistant fisheye: the ray through pixel centre (row i, col j) makes the angle ``rho * fov/2`` with the optical
     axis, ``rho`` = distance from the image centre in units of half the image height.  Scene: ground plane z =
     ground_z textured with checker squares of side ``checker_size`` (parity of floor(x/s) + floor(y/s)), uniform sky,
     opaque spheres (x, y, z, radius); the nearest hit wins; pixels beyond a polar angle of pi are black."""
-    f = np.float32
+    f = dtype
     i, j = np.mgrid[0:height, 0:width]
     u = ((j.astype(f) + f(0.5) - f(0.5 * width)) * f(2.0 / height)).astype(f)
     v = ((i.astype(f) + f(0.5) - f(0.5 * height)) * f(2.0 / height)).astype(f)
@@ -212,10 +220,10 @@ def render_eye_frames(cam_pos, cam_mat, height, width, fov_deg, checker_size, gr
         t_hit = np.full((height, width), np.inf, dtype=f)
         m_hit = np.zeros((height, width), dtype=np.int64)
         for _ in range(MAX_TERRAIN_CELLS):
-            tprobe = (tcur + f(TERRAIN_EPS)).astype(f)
+            tprobe = (tcur + np.maximum(f(TERRAIN_EPS), tcur * f(TERRAIN_EPS_REL))).astype(f)
             px = (cam[0] + tprobe * d[..., 0]).astype(f)
             py = (cam[1] + tprobe * d[..., 1]).astype(f)
-            x0, x1, y0, y1, h = terrain_cell(kind, tp, np.where(live, px, 0), np.where(live, py, 0))
+            x0, x1, y0, y1, h = terrain_cell(kind, tp, np.where(live, px, 0), np.where(live, py, 0), dtype=f)
             h = (h + f(ground_z)).astype(f)
             z_in = (cam[2] + tcur * d[..., 2]).astype(f)
             wall = live & (z_in < h - f(TERRAIN_WALL_TOL))
@@ -247,16 +255,17 @@ def render_eye_frames(cam_pos, cam_mat, height, width, fov_deg, checker_size, gr
         mat = np.where(ok, 5 + s, mat)
         tbest = np.where(ok, ts, tbest)
     for cap in capsules:                                       # the fly's own body: (p0, p1, radius) in world coordinates
-        tcap = _ray_capsule(d, np.asarray(cap[0], dtype=f) - cam, np.asarray(cap[1], dtype=f) - cam, cap[2])
+        tcap = _ray_capsule(d, np.asarray(cap[0], dtype=f) - cam, np.asarray(cap[1], dtype=f) - cam, cap[2], dtype=f)
         ok = tcap < tbest
         mat = np.where(ok, 4, mat)
         tbest = np.where(ok, tcap, tbest)
     # materials: 0 sky, 1 / 2 ground checker, 3 terrain side wall, 4 own body, 5.. spheres, -1 black
-    mat = np.where(theta > f(3.14159265), -1, mat)
+    mat = np.where(theta > f(np.pi), -1, mat)                  # (float32(pi) is the kernel's 3.14159265f)
     palette = np.zeros((6 + max(len(sphere_rgb), 0), 3), dtype=np.uint8)      # [0] black, [1 + m] material m
     palette[1] = sky_rgb
     palette[2], palette[3] = ground_rgb[0], ground_rgb[1]
     palette[4], palette[5] = wall_rgb, body_rgb
     for s, c in enumerate(sphere_rgb):
         palette[6 + s] = c
-    return palette[mat + 1]
+    frame = palette[mat + 1]
+    return (frame, mat) if return_materials else frame

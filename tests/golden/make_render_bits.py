@@ -7,7 +7,10 @@ Run on an MI355X against a build of the commit whose frames are the reference (N
 The poses (seg_xpos / seg_xquat of 2 worlds per world class) are those after the 250-step tumble of
 tests/test_sensors.py::test_eye_renderer_sees_the_simulated_world.  tests/test_render_bits_gpu.py writes them back into the
 batch and does not step, so the digests depend on the renderers only.  `render_digests` is the one definition of the cases;
-the test calls it too.  The digests are never re-recorded from the code under test."""
+the test calls it too.  The digests are never re-recorded from the code under test — with one exception on record: the eye digests of
+the gapped, blocks and mixed worlds are those of the build that made the relief walk's probe step relative beyond 210 mm (a fix of
+the drawing itself, checked against the float64 specification by tests/test_eye_parity_gpu.py; frames of the build before it differ
+in 2 to 38 pixels each, all within 15 rows of the horizon)."""
 from __future__ import annotations
 
 import hashlib

@@ -106,38 +106,11 @@ def test_odor_sensors_match_numpy(bench_model):
 
 
 def test_eye_render_oracle_known_answers():
-    """The renderer's specification (oracle/sensors_oracle.py::render_eye_frames) against geometry worked by hand."""
-    import sensors_oracle as so
+    """The renderer's specification (oracle/sensors_oracle.py::render_eye_frames) against geometry worked by hand
+    (tests/eye_parity.py::check_known_answers, which the float64 flavour passes too)."""
+    import eye_parity
 
-    H, W, fov, h = 512, 450, 157.0, 2.0
-    sky, ground = (140, 178, 230), ((77, 77, 77), (102, 102, 102))
-    down = np.eye(3)                                                    # camera axes = world axes: looks along -z (down)
-    fr = so.render_eye_frames((0.5, 0.5, h), down, H, W, fov, 4.0, 0.0, sky, ground)
-    assert fr.shape == (H, W, 3) and fr.dtype == np.uint8
-    # straight below (0.5, 0.5): square (0, 0) -> parity 0 -> colour A; the image centre is between 4 pixels
-    assert (fr[255:257, 224:226] == ground[0]).all()
-    # along the middle row a pixel at rho sees the ground at x = 0.5 + h tan(rho * fov / 2): check a few columns
-    for col in (260, 300, 330, 360, 400):
-        rho = (col + 0.5 - W / 2) * 2 / H
-        x = 0.5 + h * np.tan(rho * np.radians(fov / 2))
-        want = ground[(int(np.floor(x / 4.0)) + 0) & 1]
-        if abs(x / 4.0 - round(x / 4.0)) > 1e-3:                         # not on a checker edge
-            assert tuple(fr[256, col]) == want, col
-    # the horizon is at rho = 90 / 78.5 > 1 along the axes but inside the corners: sky only there
-    rho_corner = np.hypot(W / H, 1.0)
-    assert rho_corner * fov / 2 > 90
-    assert tuple(fr[0, 0]) == sky and tuple(fr[0, W // 2]) != sky
-    # a sphere right below: angular radius asin(r / d) -> a disc of that many pixels
-    fr2 = so.render_eye_frames((0.5, 0.5, h), down, H, W, fov, 4.0, 0.0, sky, ground, [(0.5, 0.5, 1.0, 0.4)], [(10, 20, 30)])
-    n_sphere = int((fr2 == (10, 20, 30)).all(axis=-1).sum())
-    r_pix = np.arcsin(0.4 / 1.0) / np.radians(fov / 2) * H / 2
-    assert abs(n_sphere - np.pi * r_pix ** 2) < 0.03 * np.pi * r_pix ** 2
-    # the legacy eye orientations, read as extrinsic x-y-z rotations, look forward-sideways with +z up
-    L = so.euler_xyz_extrinsic_to_mat((1.57, 0.0, -0.47))
-    Rr = so.euler_xyz_extrinsic_to_mat((-1.57, 3.14, 0.47))
-    np.testing.assert_allclose(L @ [0, 0, -1], [np.sin(0.47), np.cos(0.47), 0], atol=2e-3)
-    np.testing.assert_allclose(Rr @ [0, 0, -1], [np.sin(0.47), -np.cos(0.47), 0], atol=2e-3)
-    assert (L @ [0, 1, 0])[2] > 0.999 and (Rr @ [0, 1, 0])[2] > 0.999
+    eye_parity.check_known_answers()
 
 
 def _world_capsules(eyes, xpos_w, xquat_w):
@@ -152,43 +125,9 @@ def _world_capsules(eyes, xpos_w, xquat_w):
 
 def test_eye_render_oracle_terrain_and_body_known_answers():
     """The relief and body parts of the renderer's specification against geometry worked by hand."""
-    import sensors_oracle as so
+    import eye_parity
 
-    H, W, fov = 512, 450, 157.0
-    sky, ground, wall, body = (140, 178, 230), ((77, 77, 77), (102, 102, 102)), (51, 51, 51), (120, 90, 60)
-    down = np.eye(3)
-    gapped = (1, (1.0, 0.3, 2.0, 0.0), 0.0)
-    # straight above the middle of a 1 mm block (x = 0.5): the centre pixels see its top, i.e. the flat answer
-    flat = so.render_eye_frames((0.5, 0.5, 2.0), down, H, W, fov, 4.0, 0.0, sky, ground)
-    fr = so.render_eye_frames((0.5, 0.5, 2.0), down, H, W, fov, 4.0, 0.0, sky, ground, terrain=gapped, wall_rgb=wall)
-    assert (fr[250:262, 219:231] == flat[250:262, 219:231]).all()
-    # straight above the middle of a gap (x = 1.15, 2 mm deep, 0.3 mm wide): the centre sees the gap floor (a top surface,
-    # checker colour), a ray that leaves the gap sideways before reaching the floor sees a wall
-    fr = so.render_eye_frames((1.15, 0.5, 2.0), down, H, W, fov, 4.0, 0.0, sky, ground, terrain=gapped, wall_rgb=wall)
-    assert tuple(fr[256, 225]) in ground
-    # along the middle row (varying x): the ray with tan(angle) = 0.15 / 4 just reaches the floor's edge; beyond it -> wall
-    ang_edge = np.arctan(0.15 / 4.0)
-    col_edge = W / 2 + ang_edge / np.radians(fov / 2) * H / 2
-    assert tuple(fr[256, int(col_edge) + 3]) == wall and tuple(fr[256, int(col_edge) - 3]) in ground
-    # walls are seen only on the relief
-    assert not (flat == wall).all(axis=-1).any() and (fr == wall).all(axis=-1).mean() > 0.05
-    # blocks: above the corner of four squares each quadrant of the centre shows tops at two different levels -> the raised
-    # squares look larger (closer): count of raised-top pixels > count of low-top pixels near the centre
-    blocks = (2, (1.3, 0.35, 0.0, 0.0), 0.35)
-    frb = so.render_eye_frames((1.3, 1.3, 2.0), down, H, W, fov, 100.0, 0.0, sky, ground, terrain=blocks, wall_rgb=wall)
-    assert (frb == wall).all(axis=-1).any()
-    # a capsule along x right below the camera: its silhouette is about (length + 2 r) x 2 r at distance 1
-    cap = [((0.2, 0.5, 1.0), (0.8, 0.5, 1.0), 0.1)]
-    frc = so.render_eye_frames((0.5, 0.5, 2.0), down, H, W, fov, 4.0, 0.0, sky, ground, capsules=cap, body_rgb=body)
-    mask = (frc == body).all(axis=-1)
-    px_per_rad = H / 2 / np.radians(fov / 2)
-    want = (2 * np.arctan(0.3 / 0.9)) * (2 * np.arcsin(0.1 / 1.0)) * px_per_rad ** 2
-    assert 0.75 * want < mask.sum() < 1.15 * want
-    rows, cols = np.where(mask)
-    assert abs(rows.mean() - 255.5) < 1.0 and abs(cols.mean() - 224.5) < 1.0 and np.ptp(cols) > 2.5 * np.ptp(rows)
-    # nearest hit wins: a capsule below the ground plane is hidden
-    hidden = so.render_eye_frames((0.5, 0.5, 2.0), down, H, W, fov, 4.0, 0.0, sky, ground, capsules=[((0.2, 0.5, -1.0), (0.8, 0.5, -1.0), 0.1)], body_rgb=body)
-    assert (hidden == flat).all()
+    eye_parity.check_terrain_and_body_known_answers()
 
 
 @pytest.mark.gpu
