@@ -20,15 +20,16 @@
 #include "nmf_step.hip"
 #include "nmf_sensors.hip"
 // `#pragma clang fp reassociate(off)` at file scope holds from the first file that sets it to the end of the translation unit:
-// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip, nmf_plume.hip, nmf_taxis.hip and the host code
+// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip, nmf_plume.hip, nmf_taxis.hip, nmf_odometry.hip and the host code
 // below are all compiled under it, and the files above are not.  Which files it covers decides their kernels' arithmetic: keep the
-// order (nmf_taxis.hip adds pragmas inside its functions only: nothing of it reaches past the file).
+// order (nmf_taxis.hip and nmf_odometry.hip add pragmas inside their functions only: nothing of them reaches past the file).
 #include "nmf_eyes.hip"
 #include "nmf_camera.hip"
 #include "nmf_replay.hip"
 #include "nmf_cpg.hip"
 #include "nmf_plume.hip"
 #include "nmf_taxis.hip"
+#include "nmf_odometry.hip"
 #include "nmf_skeleton.h"      // nmf_model, the blob parser, classify_skeleton
 #endif
 
@@ -61,7 +62,7 @@ struct DeviceGuard {
   DeviceGuard guard_((b)->mem.device);                                                        \
   if (guard_.err != hipSuccess) return fail(std::string("hipSetDevice: ") + hipGetErrorString(guard_.err))
 
-// The device memory of one handle (batch, eye plan, camera plan, CPG, plume): every allocation is 16-byte granular, recorded, and freed
+// The device memory of one handle (batch, eye plan, camera plan, CPG, plume, odometry): every allocation is 16-byte granular, recorded, and freed
 // with the handle.  The first failure sets the error text, named after the entry point `who`, and sticks: later calls return
 // null without touching the device, so that a caller tests `ok` once after its last allocation.
 struct DevMem {
@@ -1543,6 +1544,100 @@ extern "C" int nmf_taxis_update(const nmf_taxis_params* p, const int16_t* centre
   hipLaunchKernelGGL(nmf::nmf_taxis_kernel, dim3((unsigned)((n_worlds + per_block - 1) / per_block)), dim3(nmf::kTaxisThreads), 0, (hipStream_t)stream,
                      A, reinterpret_cast<const int*>(centres_dev), reinterpret_cast<const float2*>(omm_dev), odor_dev, odor_gains_dev,
                      features_dev, bias_dev, drive_dev);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// ---- path integration (nmf_odometry.hip) ----
+// The shared coefficients and the per-world state; the batch lends its pose and sensor arrays to every update.
+struct nmf_odometry {
+  const nmf_batch* batch = nullptr;
+  int n_worlds = 0;
+  nmf::OdoArgs args{};
+  nmf::OdoPtrs ptrs{};
+  DevMem mem;
+};
+
+extern "C" size_t nmf_odometry_params_size(void) { return sizeof(nmf_odometry_params); }
+
+extern "C" void nmf_odometry_destroy(nmf_odometry* O) {
+  if (!O) return;
+  O->mem.release();
+  delete O;
+}
+
+extern "C" int nmf_odometry_reset(nmf_odometry* O, const uint8_t* mask_dev, const double* pose_dev, void* stream) {
+  if (!O) return fail("nmf_odometry_reset: null integrator");
+  if ((uintptr_t)pose_dev & 7) return fail("nmf_odometry_reset: pose must be 8-byte aligned");
+  DEVICE_GUARD(O);
+  hipLaunchKernelGGL(nmf::nmf_odometry_reset_kernel, dim3((unsigned)((6 * O->n_worlds + 255) / 256), (unsigned)O->args.window), dim3(256), 0,
+                     (hipStream_t)stream, O->args, O->ptrs, mask_dev, pose_dev);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+static int fill_odometry(nmf_odometry* O, const nmf_odometry_params* p, const double* coef) {
+  const nmf_batch* b = O->batch;
+  if (p->window < 1 || p->window > 4096) return fail("nmf_odometry_create: window must be in 1..4096, got " + std::to_string(p->window));
+  if (b->model->nsensor == 0 || !b->st.sensordata) return fail("nmf_odometry_create: the batch's model has no leg sensors (nsensor == 0)");
+  if (b->widths[NMF_SENSORDATA] != 96)
+    return fail("nmf_odometry_create: the batch's sensordata is " + std::to_string(b->widths[NMF_SENSORDATA]) + " wide, the update reads six leg sensors of 16 values");
+  const int nseg = b->model->nseg;
+  if (p->root_seg < 0 || p->root_seg >= nseg) return fail("nmf_odometry_create: root_seg " + std::to_string(p->root_seg) + " is outside the batch's " + std::to_string(nseg) + " segments");
+  for (int l = 0; l < 6; ++l)
+    if (p->tip_seg[l] < 0 || p->tip_seg[l] >= nseg) return fail("nmf_odometry_create: tip_seg[" + std::to_string(l) + "] = " + std::to_string(p->tip_seg[l]) + " is outside the batch's " + std::to_string(nseg) + " segments");
+  for (int l = 0; l < 6; ++l)
+    if (!(p->contact_force_threshold[l] >= 0.f) || !std::isfinite(p->contact_force_threshold[l]))
+      return fail("nmf_odometry_create: contact_force_threshold[" + std::to_string(l) + "] must be finite and not negative");
+  for (int c = 0; coef && c < 14; ++c)
+    if (!std::isfinite(coef[c])) return fail("nmf_odometry_create: coefficient " + std::to_string(c) + " is not finite");
+  nmf::OdoArgs& A = O->args;
+  A.n_worlds = O->n_worlds; A.nseg = nseg; A.root_seg = p->root_seg; A.window = p->window;
+  for (int l = 0; l < 6; ++l) { A.tip_seg[l] = p->tip_seg[l]; A.thr[l] = p->contact_force_threshold[l]; }
+  A.inv_window = 1.0 / (double)p->window;
+  const size_t n = (size_t)O->n_worlds;
+  nmf::OdoPtrs& P = O->ptrs;
+  P.seg_xpos = b->st.seg_xpos; P.seg_xquat = b->st.seg_xquat; P.sensordata = b->st.sensordata;
+  P.coef = (const double*)O->mem.upload(coef, sizeof(double) * 14);
+  P.count = (int*)O->mem.alloc(sizeof(int) * n);
+  P.xprev = (float*)O->mem.alloc(sizeof(float) * 6 * n);
+  P.cprev = (uint8_t*)O->mem.alloc(6 * n);
+  P.total = (double*)O->mem.alloc(sizeof(double) * 6 * n);
+  P.win = (double*)O->mem.alloc(sizeof(double) * 6 * n);
+  P.heading = (double*)O->mem.alloc(sizeof(double) * n);
+  P.position = (double*)O->mem.alloc(sizeof(double) * 2 * n);
+  P.home = (double*)O->mem.alloc(sizeof(double) * 2 * n);
+  P.ring = (double*)O->mem.alloc(sizeof(double) * 6 * n * (size_t)p->window);
+  if (!O->mem.ok) return -1;
+  if (nmf_odometry_reset(O, nullptr, nullptr, nullptr) != 0) return -1;
+  HIP_OK(hipDeviceSynchronize());
+  return 0;
+}
+
+extern "C" nmf_odometry* nmf_odometry_create(nmf_batch* b, const nmf_odometry_params* p, const double* coef) {
+  if (!b || !p) { fail("nmf_odometry_create: null batch / params"); return nullptr; }
+  return build_or_destroy(b->mem.device, "nmf_odometry_create", new nmf_odometry(), nmf_odometry_destroy, [&](nmf_odometry* O) {
+    O->n_worlds = b->n_worlds; O->batch = b;
+    return fill_odometry(O, p, coef);
+  });
+}
+
+extern "C" void* nmf_odometry_field_ptr(nmf_odometry* O, int which, int32_t* width) {
+  if (!O) { fail("nmf_odometry_field_ptr: null integrator"); return nullptr; }
+  const nmf::OdoPtrs& P = O->ptrs;
+  void* ptr[7] = {P.total, P.win, P.heading, P.position, P.home, P.count, const_cast<double*>(P.coef)};
+  const int32_t w[7] = {6, 6, 1, 2, 2, 1, 14};
+  if (which < 0 || which > 6) { fail("nmf_odometry_field_ptr: no such field"); return nullptr; }
+  if (width) *width = w[which];
+  return ptr[which];
+}
+
+// Pure stream-ordered work: one kernel launch.
+extern "C" int nmf_odometry_update(nmf_odometry* O, void* stream) {
+  if (!O) return fail("nmf_odometry_update: null integrator");
+  DEVICE_GUARD(O);
+  hipLaunchKernelGGL(nmf::nmf_odometry_update_kernel, dim3((unsigned)((O->n_worlds + nmf::kOdoWorlds - 1) / nmf::kOdoWorlds)), dim3(nmf::kOdoThreads),
+                     0, (hipStream_t)stream, O->args, O->ptrs);
   HIP_OK(hipGetLastError());
   return 0;
 }

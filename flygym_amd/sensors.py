@@ -13,9 +13,11 @@ names (``:199-200``) are not shipped, and no code exists, so the following is *b
 * a reading is the mean of the cell's pixels in its channel / 255, stored in channel 0 (yellow) or 1 (pale);
 * odor intensity = sum over sources of ``peak / distance**2`` at the four sensor sites (:class:`OdorSensors`), or the reading
   of a time-varying plume grid per world, advected by a noisy wind beside the physics (:class:`OdorPlume`; the reference holds
-  no plume code or data: the whole model is stated in include/nmf.h and specified by tests/plume_spec.py).
+  no plume code or data: the whole model is stated in include/nmf.h and specified by tests/plume_spec.py);
+* path integration (:class:`PathIntegrator`) — heading and position from the legs' stance strides, in the form of flygym 1.x's
+  path-integration task — is stated in include/nmf.h and specified by tests/odometry_spec.py.
 
-The arithmetic runs in ``libnmf_hip.so`` (``nmf_retina_resample``, ``nmf_odor_intensity``, ``nmf_plume_*``).
+The arithmetic runs in ``libnmf_hip.so`` (``nmf_retina_resample``, ``nmf_odor_intensity``, ``nmf_plume_*``, ``nmf_odometry_*``).
 """
 
 from __future__ import annotations
@@ -26,7 +28,7 @@ import numpy as np
 
 from . import _native
 
-__all__ = ["Retina", "OdorSensors", "OdorPlume", "RAW_IMG_HEIGHT", "RAW_IMG_WIDTH", "NUM_OMMATIDIA"]
+__all__ = ["Retina", "OdorSensors", "OdorPlume", "PathIntegrator", "RAW_IMG_HEIGHT", "RAW_IMG_WIDTH", "NUM_OMMATIDIA"]
 
 RAW_IMG_HEIGHT = 512     # flygym1_config.yaml:143
 RAW_IMG_WIDTH = 450      # :144
@@ -370,3 +372,185 @@ class OdorPlume:
         _native.check(_native.lib().nmf_plume_sample_sites(h, self._seg.data_ptr(), self._rel.data_ptr(), 4, out.data_ptr(),
                                                            self.out_of_bounds.data_ptr(), self.sim._stream()))
         return out
+
+
+class _OdometryParams(ctypes.Structure):
+    """``nmf_odometry_params`` of include/nmf.h."""
+
+    _fields_ = [("window", ctypes.c_int32), ("root_seg", ctypes.c_int32), ("tip_seg", ctypes.c_int32 * 6),
+                ("contact_force_threshold", ctypes.c_float * 6)]
+
+
+class PathIntegrator:
+    """Path integration on the GPU (``nmf_odometry_*``): the fly's heading and position estimated from proprioception alone, from
+    how far each leg's tip travels relative to the body while the leg is on the ground.
+
+    Build-defined (the reference ships no path integration), in the form of flygym 1.x's path-integration task; the statement of
+    the model is include/nmf.h (``nmf_odometry_update``), its specification in numpy tests/odometry_spec.py.  One :meth:`update`
+    per control tick, from the batch's ``seg_xpos`` / ``seg_xquat`` / ``sensordata`` as they stand when it starts::
+
+        x_l = (tip_l - root) . xhat                       (xhat: the root segment's x axis; float32)
+        c_l = found_l > 0 and (thr_l == 0 or |F_l| > thr_l)
+        total_l += x_l(previous update) - x_l             while the leg is on the ground in both updates
+        win_l = total_l - total_l(``window`` updates ago)
+        dh = (heading_bias + sum_l heading_coef_l win_l) / window,  dd = (disp_bias + sum_l disp_coef_l win_l) / window
+        heading <- wrap(heading + dh);  position <- position + dd (cos heading, sin heading)        once ``window`` updates are in
+        home = -R(heading)^T position                     (the way back to the estimate's origin, in the body frame)
+
+    The first update after a reset only primes the tip coordinates; the estimates stand still for the first ``window`` updates,
+    as flygym 1.x's.  A pose that is not finite stays in that world's state until the world is reset.
+
+    Args:
+        sim: the batch; for a world with several flies ``sim.for_fly(fly_name)``.
+        fly_name: the fly whose legs are read.
+        window: updates a stride window spans (1..4096).
+        contact_force_thresholds: per leg position ``(f, m, h)``, in the contact sensors' force unit; 0 counts every contact.
+        coefficients: 14 values in the device's order — ``heading_coef[6]``, ``disp_coef[6]`` (legs in ``LEGS`` order),
+            ``heading_bias``, ``disp_bias`` —, e.g. from :meth:`calibrate`; default zeros.
+
+    ``stride_total`` and ``window_strides`` ``(n, 6)``, ``heading`` ``(n,)``, ``position`` and ``home`` ``(n, 2)`` float64,
+    ``count`` ``(n,)`` int32 and ``coefficients`` ``(14,)`` float64 (shared by all worlds) are zero-copy views of the device state,
+    writable between launches.  Every method is stream-ordered device work on the simulation's stream; :meth:`update` is one
+    launch and can be captured in a graph after the tick's last step.  Close the integrator before its simulation.
+    """
+
+    def __init__(self, sim, fly_name: str, *, window: int, contact_force_thresholds=(0.0, 0.0, 0.0), coefficients=None):
+        from .anatomy import LEGS
+        from .simulation import _field_view, _tensor_from_ptr
+
+        if hasattr(sim, "for_fly"):
+            raise ValueError(f"a world with several flies has one batch per fly: pass sim.for_fly({fly_name!r})")
+        if fly_name not in sim.world.fly_lookup:
+            raise ValueError(f"no fly named {fly_name!r} in this simulation ({', '.join(sim.world.fly_lookup)})")
+        if len(contact_force_thresholds) != 3:
+            raise ValueError(f"contact_force_thresholds takes one value for each of 'f', 'm', 'h', got {contact_force_thresholds!r}")
+        self.sim, self.fly_name = sim, fly_name
+        self.n_worlds, self.window = int(sim.n_worlds), int(window)
+        fly = sim.world.fly_lookup[fly_name]
+        segs = [s.name for s in fly.get_bodysegs_order()]
+        self.root_seg = segs.index(fly.root_segment.name)
+        self.tip_seg = np.array([segs.index(f"{leg}_tarsus5") for leg in LEGS], dtype=np.int32)
+        by_pos = dict(zip("fmh", (float(v) for v in contact_force_thresholds)))
+        self.contact_force_thresholds = np.array([by_pos[leg[1]] for leg in LEGS], dtype=np.float32)
+        coef = None
+        if coefficients is not None:
+            coef = np.ascontiguousarray(coefficients, dtype=np.float64).reshape(-1)
+            if coef.size != 14:
+                raise ValueError(f"coefficients takes 14 values (heading_coef[6], disp_coef[6], heading_bias, disp_bias), got {coef.size}")
+        lib = _native.lib()
+        if ctypes.sizeof(_OdometryParams) != lib.nmf_odometry_params_size():
+            raise _native.NativeError("nmf_odometry_params layout mismatch between sensors.py and libnmf_hip.so")
+        self._params = _OdometryParams(self.window, self.root_seg, (ctypes.c_int32 * 6)(*self.tip_seg.tolist()),
+                                       (ctypes.c_float * 6)(*self.contact_force_thresholds.tolist()))
+        self._h = lib.nmf_odometry_create(sim._batch_h, ctypes.byref(self._params), None if coef is None else coef.ctypes.data)
+        if not self._h:
+            raise _native.NativeError(lib.nmf_last_error().decode())
+        view = lambda which, typestr="<f8": _field_view(sim, lib.nmf_odometry_field_ptr, self._h, which, typestr)
+        self.stride_total, self.window_strides = view(0), view(1)
+        self.heading, self.position, self.home = view(2).reshape(self.n_worlds), view(3), view(4)
+        self.count = view(5, "<i4").reshape(self.n_worlds)
+        self.coefficients = _tensor_from_ptr(sim._torch, lib.nmf_odometry_field_ptr(self._h, 6, None), (14,), sim.device, "<f8")
+
+    # ---- lifecycle
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _native.lib().nmf_odometry_destroy(self._h)
+            self._h = None
+            self.stride_total = self.window_strides = self.heading = self.position = self.home = None      # (views of freed memory)
+            self.count = self.coefficients = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _handle(self):
+        if not getattr(self, "_h", None):
+            raise RuntimeError("the integrator is closed")
+        return self._h
+
+    # ---- the estimate
+    def update(self) -> None:
+        """One update of every world from the batch's current pose and sensor outputs (one launch; no host sync)."""
+        _native.check(_native.lib().nmf_odometry_update(self._handle(), self.sim._stream()))
+
+    def reset(self, mask=None, pose=None) -> None:
+        """The worlds of ``mask`` (``(n_worlds,)`` bool, numpy or torch; default all) forget their strides and start again, priming
+        included, from ``pose`` (``(n_worlds, 3)`` x, y, heading, numpy or torch; default zeros; the rows of the other worlds are
+        not read); the others keep their state."""
+        h = self._handle()
+        t = self.sim._torch
+        m = p = None
+        if mask is not None:
+            m = t.as_tensor(mask, device=self.sim.device)
+            if tuple(m.shape) != (self.n_worlds,):
+                raise ValueError(f"Expected a reset mask of shape ({self.n_worlds},), but got {tuple(m.shape)}")
+            m = (m != 0).to(t.uint8).contiguous()
+        if pose is not None:
+            p = t.as_tensor(pose)
+            if tuple(p.shape) != (self.n_worlds, 3):
+                raise ValueError(f"Expected a pose of shape ({self.n_worlds}, 3), but got {tuple(p.shape)}")
+            p = p.to(device=self.sim.device, dtype=t.float64).contiguous()
+        _native.check(_native.lib().nmf_odometry_reset(h, None if m is None else m.data_ptr(), None if p is None else p.data_ptr(),
+                                                       self.sim._stream()))
+
+    def set_coefficients(self, heading_coef, disp_coef, heading_bias: float = 0.0, disp_bias: float = 0.0) -> None:
+        """Six heading and six displacement coefficients (legs in ``LEGS`` order) and the two biases: copied into
+        :attr:`coefficients` on the simulation's stream."""
+        self._handle()
+        coef = np.concatenate([np.asarray(heading_coef, dtype=np.float64).reshape(-1), np.asarray(disp_coef, dtype=np.float64).reshape(-1),
+                               [float(heading_bias), float(disp_bias)]])
+        if coef.size != 14:
+            raise ValueError("heading_coef and disp_coef take six values each")
+        if not np.isfinite(coef).all():
+            raise ValueError("the coefficients must be finite")
+        self.coefficients.copy_(self.sim._torch.as_tensor(coef).to(self.sim.device))
+
+    def true_pose(self):
+        """``(n_worlds, 3)`` float64 on the device: x, y and heading (the direction of the x axis in the ground plane) of the root
+        segment, from the poses of the last step: what the estimate is compared with and calibrated against."""
+        self._handle()
+        t = self.sim._torch
+        xpos = self.sim.field("seg_xpos").reshape(self.n_worlds, -1, 3)[:, self.root_seg].to(t.float64)
+        qw, qx, qy, qz = self.sim.field("seg_xquat").reshape(self.n_worlds, -1, 4)[:, self.root_seg].to(t.float64).unbind(dim=1)
+        heading = t.atan2(2.0 * (qx * qy + qw * qz), 1.0 - 2.0 * (qy * qy + qz * qz))
+        return t.stack([xpos[:, 0], xpos[:, 1], heading], dim=1)
+
+    @staticmethod
+    def calibrate(window_strides_trace, pose_trace, window: int):
+        """Least-squares coefficients from a recorded walk: ``window_strides_trace`` ``(T, n, 6)`` (:attr:`window_strides` after
+        every update) and ``pose_trace`` ``(T, n, 3)`` (:meth:`true_pose` at the same instants).  For every tick ``k >= window`` the
+        targets are the heading change ``wrap(h_k - h_{k - window})`` and the distance ``|p_k - p_{k - window}|`` over the window;
+        the model has flygym 1.x's structure — the heading change from the three left-minus-right differences of the pairs' window
+        strides plus a bias, the distance from the three left-plus-right sums plus a bias —, solved with ``numpy.linalg.lstsq``.
+        Returns ``(coefficients (14,) float64 in the device's order, r2_heading, r2_displacement)``."""
+        win = np.asarray(window_strides_trace, dtype=np.float64)
+        pose = np.asarray(pose_trace, dtype=np.float64)
+        W = int(window)
+        if win.ndim != 3 or win.shape[2] != 6 or pose.shape != win.shape[:2] + (3,):
+            raise ValueError(f"Expected traces of shape (T, n, 6) and (T, n, 3), but got {win.shape} and {pose.shape}")
+        if W < 1 or win.shape[0] <= W:
+            raise ValueError(f"the traces must be longer than the window ({W} updates), got {win.shape[0]}")
+        dh = pose[W:, :, 2] - pose[:-W, :, 2]
+        dh = dh - 2.0 * np.pi * np.rint(dh / (2.0 * np.pi))
+        dd = np.linalg.norm(pose[W:, :, :2] - pose[:-W, :, :2], axis=-1)
+        x = win[W:]
+        ones = np.ones(x.shape[:2] + (1,))
+        A_h = np.concatenate([x[..., :3] - x[..., 3:], ones], axis=-1).reshape(-1, 4)
+        A_d = np.concatenate([x[..., :3] + x[..., 3:], ones], axis=-1).reshape(-1, 4)
+
+        def fit(A, y):
+            sol = np.linalg.lstsq(A, y, rcond=None)[0]
+            ss = float(((y - y.mean()) ** 2).sum())
+            return sol, (1.0 - float(((y - A @ sol) ** 2).sum()) / ss if ss > 0 else 1.0)
+
+        a, r2_h = fit(A_h, dh.reshape(-1))
+        b, r2_d = fit(A_d, dd.reshape(-1))
+        return np.concatenate([a[:3], -a[:3], b[:3], b[:3], [a[3], b[3]]]), r2_h, r2_d

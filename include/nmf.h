@@ -28,6 +28,7 @@ typedef struct nmf_eye_plan nmf_eye_plan;
 typedef struct nmf_camera_plan nmf_camera_plan;
 typedef struct nmf_cpg nmf_cpg;
 typedef struct nmf_plume nmf_plume;
+typedef struct nmf_odometry nmf_odometry;
 
 /* Per-world fields addressable through nmf_field_ptr / nmf_gather_* */
 enum nmf_field {
@@ -595,6 +596,77 @@ size_t nmf_taxis_params_size(void);
 int nmf_taxis_update(const nmf_taxis_params* params, const int16_t* centres_dev, int n_omm, int height, int width,
                      const float* omm_dev, const float* odor_dev, const float* odor_gains_dev, int n_dims, int n_worlds,
                      float* features_dev, float* bias_dev, float* drive_dev, void* stream);
+
+/* Path integration with its state on the device (flygym_amd.sensors.PathIntegrator; csrc/nmf_odometry.hip): the fly's heading and
+ * position estimated from proprioception alone — how far each leg's tip travels backwards along the body's x axis while the leg is
+ * on the ground.  No reference counterpart (the snapshot holds no path integration): build-defined and pinned by nothing, in the
+ * form of flygym 1.x's path-integration task (specification tests/odometry_spec.py).
+ * State per world: count (int32, updates since the reset); per leg (LEGS order lf lm lh rf rm rh) the last body-frame fore-aft
+ * coordinate xprev (float32), the last contact flag cprev and the cumulative stride total (float64); a ring of the last `window`
+ * totals (float64); the estimates heading (float64, radians, kept in [-pi, pi]) and position[2] (float64).  Shared by all worlds of
+ * a handle, in device memory and writable between launches: 14 float64 coefficients in the order heading_coef[6], disp_coef[6],
+ * heading_bias, disp_bias.  One update (one launch per control tick) reads the batch's seg_xpos, seg_xquat and sensordata as they
+ * stand when it starts; every right-hand side is taken from the old state:
+ *   xhat   = the root segment's x axis: (1 - 2 (qy qy + qz qz), 2 (qx qy + qw qz), 2 (qx qz - qw qy)) of its quaternion, float32
+ *   x_l    = fl(fl(fl(dx ax) + fl(dy ay)) + fl(dz az)),  d = position of tip_seg[l] - position of root_seg        (float32)
+ *   c_l    = found_l > 0 and (thr_l == 0 or fl(fl(fx^2 + fy^2) + fz^2) > fl(thr_l^2))      (sensor l's values 0..3; |F| does not
+ *                                                                                            depend on the frame it is reported in)
+ *   inc_l  = (count > 0 and c_l and cprev_l) ? (double) fl(xprev_l - x_l) : 0     (stance moves the tip backwards: positive when
+ *                                                                                   walking forwards)
+ *   total_l <- total_l + inc_l                                                                                    (float64)
+ *   slot   = count mod window;  win_l = total_l(new) - ring[slot][l];  ring[slot][l] <- total_l(new)
+ *   valid  = count >= window                                  (win then spans exactly `window` updates)
+ *   dh = heading_bias + sum_{l = 0..5} heading_coef_l win_l,  dd = disp_bias + sum_l disp_coef_l win_l   (float64, ascending l)
+ *   dh, dd <- dh inv_window, dd inv_window                    (inv_window = 1.0 / window, computed once on the host in float64)
+ *   if valid: heading <- wrap(heading + dh),  wrap(h) = h - 2 pi rint(h (1 / 2 pi))    (the float64 constants 6.283185307179586
+ *                                                                                        and 0.15915494309189535; also applied
+ *                                                                                        to a reset's heading)
+ *   (s, c) = sine and cosine of (float) heading(new) — the heading rounded to float32 —, evaluated in float64 (within 2e-15 of
+ *            the exact ones: position and home stay within 1e-7 of the distance covered of a float64 evaluation of these lines)
+ *   if valid: position <- position + dd (c, s)                                                                    (float64)
+ *   home   = (-(c px + s py), -(-s px + c py)) of the new position: the way back to the estimate's origin in the body frame
+ *   xprev_l <- x_l, cprev_l <- c_l, count <- count + 1
+ * Every product, sum and difference above is rounded on its own (no contraction, no reassociation) and nothing is divided, so the
+ * state equals the specification's bit for bit up to the sine and cosine.  The first update after a reset only primes xprev and
+ * cprev; during the first `window` updates the estimates stand still (flygym 1.x likewise starts estimating after one window).
+ * A pose that is not finite propagates into that world's state until the world is reset. */
+typedef struct nmf_odometry_params {
+  int32_t window;               /* updates a stride window spans (1..4096)                                               */
+  int32_t root_seg;             /* index of the body's root segment in the batch's segment order                         */
+  int32_t tip_seg[6];           /* per leg: the segment whose origin is the leg's tip                                    */
+  float contact_force_threshold[6];   /* per leg: the leg is on the ground when |F| exceeds it (0: whenever found > 0)    */
+} nmf_odometry_params;
+
+/* sizeof(nmf_odometry_params) as this library was compiled (as nmf_eye_params_size). */
+size_t nmf_odometry_params_size(void);
+
+/* An explicit handle for the worlds of `batch`, on its device.  coef_host: the 14 float64 coefficients in HOST memory, or NULL for
+ * zeros.  Owns the state arrays and resets every world (nmf_odometry_reset with NULL mask and pose).  NOT stream-ordered
+ * (allocations, synchronous uploads); must not be called inside a stream capture.  NULL on error (nmf_last_error), with nothing
+ * left allocated: window outside 1..4096; root_seg or a tip_seg outside the batch's segments; a threshold that is negative or not
+ * finite; a coefficient that is not finite; a batch whose model has no six leg sensors (as nmf_cpg_hybrid_enable); no device
+ * memory.  The handle keeps pointers to the batch's seg_xpos / seg_xquat / sensordata arrays: destroy it before the batch. */
+nmf_odometry* nmf_odometry_create(nmf_batch* batch, const nmf_odometry_params* params, const double* coef_host);
+void nmf_odometry_destroy(nmf_odometry* odometry);
+
+/* The worlds with mask_dev[w] != 0 (uint8 per world, device memory; NULL: all) get count = 0, totals, window strides and ring rows
+ * 0, no previous sample (the next update primes again), and the estimate pose_dev[w] = (x, y, heading) (float64
+ * [n_worlds][3], device memory; NULL: zeros) with the home vector that belongs to it; the others are not touched.  Stream-ordered. */
+int nmf_odometry_reset(nmf_odometry* odometry, const uint8_t* mask_dev, const double* pose_dev, void* stream);
+
+/* One update of every world: ONE kernel launch on `stream`, no allocation, no host synchronisation, hipGraph-capturable (count
+ * lives on the device, so a captured update replays correctly any number of times). */
+int nmf_odometry_update(nmf_odometry* odometry, void* stream);
+
+/* Device pointer + row width of an array of the handle (zero-copy views; writable between launches). */
+#define NMF_ODOMETRY_TOTAL 0      /* [6] float64: cumulative stride per leg                                   */
+#define NMF_ODOMETRY_WINDOW 1     /* [6] float64: win of the last update                                      */
+#define NMF_ODOMETRY_HEADING 2    /* [1] float64                                                              */
+#define NMF_ODOMETRY_POSITION 3   /* [2] float64                                                              */
+#define NMF_ODOMETRY_HOME 4       /* [2] float64                                                              */
+#define NMF_ODOMETRY_COUNT 5      /* [1] int32                                                                */
+#define NMF_ODOMETRY_COEF 6       /* ONE row of 14 float64 shared by all worlds (width 14; not per world)     */
+void* nmf_odometry_field_ptr(nmf_odometry* odometry, int which, int32_t* width);
 
 /* Odor intensity at n_sensors points rigidly attached to named segments (sensor_seg = index into the
  * batch's segment order, sensor_rel = offset in the segment frame): out[w][d][k] = sum_s peak[s][d] / dist^2.
