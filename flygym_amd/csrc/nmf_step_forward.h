@@ -402,6 +402,40 @@ __device__ bool physics_forward(FlyLds<TP>& s, const GModel& m, int lane, const 
     }
     STAGE(8);
     for (int iter = 0; iter < m.max_iter; ++iter) {
+      // Tethered worlds: after a move the gradient is evaluated afresh from the qacc and the row residuals the loop holds, as the
+      // oracle does, not carried.  The Euler step solves (M + hB) a = qfrc_smooth + JT f = M qacc − grad with the forces of
+      // those residuals, so what is left of their gradient enters the new velocity through M⁻¹, not through H⁻¹, and the weld
+      // rows make H = M + JT D J stiffer than M by d / (1 − d) = 49..99 in the root's directions.  The first move from the
+      // unconstrained acceleration changes the row forces by that factor times the forces that remain; a gradient carried
+      // through it keeps that change's rounding (and its floor, in magv), and the loop ended there with M⁻¹ grad at 1e-5..1e-4 of
+      // the step's acceleration where the float32 oracle makes a second move.  Evaluated afresh the gradient is that of the
+      // forces the Euler step will read, and the second move takes it down to rounding.
+      if constexpr (WELD) {
+        if (iter > 0) {
+          if (red) {
+            if constexpr (TP::kStar) { if constexpr (TP::REST_B > 0) {
+              for (int j = lane; j < TP::NV; j += kWave) search[j] = (j >= 6 && j < TP::LD0) ? 0.f : s.qacc[j] - s.qacc_smooth[j];
+            } }
+            WSYNC();
+            mul_M(s, search, m, lane, false, [&](int j, float v) { Gv[j] = v; });
+          } else {
+            WSYNC();
+            mul_M(s, s.qacc, m, lane, false, [&](int j, float v) { Gv[j] = v - s.qfrc_smooth[j]; });
+          }
+          WSYNC();
+          float f0[4] = {0.f, 0.f, 0.f, 0.f};
+          if (c.on) contact_row_forces(c, -1.f, f0);
+          gn = 0.f; gm = 0.f;
+          contact_project<TP, false>(s, c, wr, fr, f0, wr.D * wr.jar, 0.f, m, lane, walls, [&](int j, float proj) {
+            const float gv = Gv[j], qs = s.qfrc_smooth[j];
+            const float gj = gv + proj;
+            const float mag = fabsf(gv + qs) + fabsf(qs) + fabsf(proj);
+            rhs[j] = -gj; magv[j] = mag;
+            gn += gj * gj; gm += mag * mag;
+          });
+          gn = wave_sum(gn); gm = wave_sum(gm);
+        }
+      }
       // converged, or the gradient is at its float32 rounding-noise floor (oracle: NMF_NOISE_FACTOR)
       if (scale * sqrtf(gn) < m.tolerance || sqrtf(gn) <= kNoiseFactor * 1.1920929e-07f * sqrtf(gm)) break;
       STAGE(9);

@@ -259,7 +259,8 @@ def test_legs_active_only_skeleton_parity(torch_mod, oracle_lib):
 def test_tethered_world_parity(torch_mod, oracle_lib, preset):
     """TetheredWorld (reference compose/world.py:334-366): the root is held by a soft 6-row weld.  The fixture
     mirrors the reference's tests/conftest.py (LEGS_ONLY, YPR, 42 position actuators kp 50, adhesion, spawn z 1.5);
-    ALL_BIOLOGICAL takes the same weld through the general-tree kernel."""
+    ALL_BIOLOGICAL takes the same weld through the general-tree kernel.
+    (The root stays at the anchor of an identity spawn here; ``test_tethered_gpu.py`` covers a rotated spawn and roots off it.)"""
     torch = torch_mod
     from flygym_amd import HIPSimulation, anatomy as A
     from flygym_amd.compose import ActuatorType, Fly, KinematicPosePreset, TetheredWorld
