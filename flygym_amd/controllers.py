@@ -44,9 +44,9 @@ import ctypes
 import numpy as np
 
 from . import _native
+from ._handle import NativeHandle, _field_view, check_params, fly_batch, leg_segments, reset_mask
 from .anatomy import LEGS, JointDOF
 from .replay import MotionSnippet
-from .simulation import _field_view
 
 __all__ = ["TripodCPG", "TurningCPG", "HybridTurningCPG", "SensorySteering"]
 
@@ -195,7 +195,7 @@ class _CpgParams(ctypes.Structure):
                 ("adhesion_off", ctypes.c_float), ("table_steps", ctypes.c_int32)]
 
 
-class TurningCPG(TripodCPG):
+class TurningCPG(NativeHandle, TripodCPG):
     """Closed-loop tripod CPG of one fly of a :class:`~flygym_amd.HIPSimulation`, advanced on the GPU (``nmf_cpg_advance``).
 
     Per step and world (every right-hand side from the old state; the row is computed before the update)::
@@ -216,11 +216,11 @@ class TurningCPG(TripodCPG):
     """
 
     _advance_entry = "nmf_cpg_advance"                   # the library entry point behind :meth:`advance`
+    _destroy_entry, _noun, _views = "nmf_cpg_destroy", "controller", ("phase", "magnitude", "drive")
 
     def __init__(self, sim, fly_name: str, *, frequency: float = 12.0, coupling: float = 10.0, convergence: float = 20.0,
                  n_phase_bins: int = 256, adhesion=None, table_steps: int = 64):
-        if hasattr(sim, "for_fly"):
-            raise ValueError(f"a world with several flies has one batch per fly: pass sim.for_fly({fly_name!r})")
+        sim = fly_batch(sim, fly_name, resolve=False)
         if fly_name not in sim.world.fly_lookup:
             raise ValueError(f"no fly named {fly_name!r} in this simulation ({', '.join(sim.world.fly_lookup)})")
         if int(table_steps) < 1:
@@ -243,47 +243,19 @@ class TurningCPG(TripodCPG):
         self.n_act = n_pos + (6 if adhesion is not None else 0)
         if int(self.act_ids.numel()) != self.n_act:
             raise ValueError(f"the fly has {int(self.act_ids.numel())} actuators for a table of {self.n_act} columns")
-        lib = _native.lib()
-        if ctypes.sizeof(_CpgParams) != lib.nmf_cpg_params_size():
-            raise _native.NativeError("nmf_cpg_params layout mismatch between controllers.py and libnmf_hip.so")
+        check_params(_CpgParams, "nmf_cpg_params_size", "controllers.py")
         on, off = self.adhesion or (0.0, 0.0)
         self._params = _CpgParams(n_pos, self.n_bins, self.frequency, self.timestep, self.coupling, self.convergence, on, off,
                                   self.table_steps)
         cycle = np.ascontiguousarray(self.cycle, dtype=np.float32)
         legs = np.ascontiguousarray(self.leg_of_dof, dtype=np.int32)
         stance = None if self.stance is None else np.ascontiguousarray(self.stance, dtype=np.uint8)
-        self._h = lib.nmf_cpg_create(sim._batch_h, ctypes.byref(self._params), cycle.ctypes.data, legs.ctypes.data,
-                                     None if stance is None else stance.ctypes.data)
-        if not self._h:
-            raise _native.NativeError(lib.nmf_last_error().decode())
-        self.phase, self.magnitude, self.drive = (_field_view(sim, lib.nmf_cpg_field_ptr, self._h, which, typestr)
+        self._create("nmf_cpg_create", sim._batch_h, ctypes.byref(self._params), cycle.ctypes.data, legs.ctypes.data,
+                     None if stance is None else stance.ctypes.data)
+        self.phase, self.magnitude, self.drive = (_field_view(sim, _native.lib().nmf_cpg_field_ptr, self._h, which, typestr)
                                                   for which, typestr in ((0, "<f8"), (1, "<f4"), (2, "<f4")))
         t = sim._torch
         self.table = t.zeros((self.n_worlds, self.table_steps, self.n_act), dtype=t.float32, device=sim.device)
-
-    # ---- lifecycle
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _native.lib().nmf_cpg_destroy(self._h)
-            self._h = None
-            self.phase = self.magnitude = self.drive = None        # (views of freed memory)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _handle(self):
-        if not getattr(self, "_h", None):
-            raise RuntimeError("the controller is closed")
-        return self._h
 
     # ---- control
     def set_drive(self, drive) -> None:
@@ -301,16 +273,10 @@ class TurningCPG(TripodCPG):
         ``theta_l = ((first_world + w) / total_worlds + b_l / 2 pi) mod 1``, ``r = 1``, ``drive = (1, 1)``; the others keep their
         state.  Stream-ordered device work (no host sync)."""
         h = self._handle()
-        t = self.sim._torch
         total = self.n_worlds if total_worlds is None else int(total_worlds)
         if int(first_world) < 0 or int(first_world) + self.n_worlds > total:
             raise ValueError(f"worlds {first_world}..{int(first_world) + self.n_worlds - 1} do not lie inside a population of {total}")
-        m = None
-        if mask is not None:
-            m = t.as_tensor(mask, device=self.sim.device)
-            if tuple(m.shape) != (self.n_worlds,):
-                raise ValueError(f"Expected a reset mask of shape ({self.n_worlds},), but got {tuple(m.shape)}")
-            m = (m != 0).to(t.uint8).contiguous()
+        m = reset_mask(mask, self.n_worlds, self.sim)
         _native.check(_native.lib().nmf_cpg_reset(h, None if m is None else m.data_ptr(), int(first_world), total, self.sim._stream()))
 
     def advance(self, n_steps: int):
@@ -380,6 +346,7 @@ class HybridTurningCPG(TurningCPG):
     """
 
     _advance_entry = "nmf_cpg_advance_hybrid"
+    _views = TurningCPG._views + ("retraction", "stumbling", "rule_flags")
 
     def __init__(self, sim, fly_name: str, *, retraction_threshold: float = 0.05, stumbling_force_threshold: float = STUMBLING_DEFAULT,
                  retraction_rates=(800.0, 700.0), stumbling_rates=(2200.0, 1800.0), max_correction: float = 80.0,
@@ -422,21 +389,14 @@ class HybridTurningCPG(TurningCPG):
         # swing: the complement of the stance bins, whether or not the table has adhesion columns
         stance = self.stance if self.stance is not None else self.stance_bins(sim.model, fly)
         self.swing = np.ascontiguousarray(~np.asarray(stance, dtype=bool), dtype=np.uint8)
-        segs = [s.name for s in fly.get_bodysegs_order()]
-        self.root_seg = segs.index(fly.root_segment.name)
-        self.tip_seg = np.array([segs.index(f"{leg}_tarsus5") for leg in LEGS], dtype=np.int32)
-        if ctypes.sizeof(_CpgHybridParams) != lib.nmf_cpg_hybrid_params_size():
-            raise _native.NativeError("nmf_cpg_hybrid_params layout mismatch between controllers.py and libnmf_hip.so")
+        self.root_seg, self.tip_seg = leg_segments(fly, LEGS)
+        check_params(_CpgHybridParams, "nmf_cpg_hybrid_params_size", "controllers.py")
         self._hybrid_params = _CpgHybridParams(self.retraction_threshold, self.stumbling_force_threshold, *self.retraction_rates,
                                                *self.stumbling_rates, self.max_correction)
         _native.check(lib.nmf_cpg_hybrid_enable(self._h, ctypes.byref(self._hybrid_params), self.corr.ctypes.data,
                                                 self.swing.ctypes.data, self.root_seg, self.tip_seg.ctypes.data))
         self.retraction, self.stumbling, self.rule_flags = (_field_view(sim, lib.nmf_cpg_field_ptr, self._h, which, typestr)
                                                             for which, typestr in ((3, "<f4"), (4, "<f4"), (5, "|u1")))
-
-    def close(self) -> None:
-        super().close()
-        self.retraction = self.stumbling = self.rule_flags = None
 
 
 class _TaxisParams(ctypes.Structure):
@@ -497,8 +457,7 @@ class SensorySteering:
                  odor_delta: float = 0.8, base: float = 1.0, drive_min: float = 0.2, drive_max: float = 1.2):
         from .sensors import Retina
 
-        if hasattr(sim, "for_fly"):          # a world with several flies: this fly's batch
-            sim = sim.for_fly(fly_name)
+        sim = fly_batch(sim, fly_name, resolve=True)
         if fly_name not in sim.world.fly_lookup:
             raise ValueError(f"no fly named {fly_name!r} in this simulation ({', '.join(sim.world.fly_lookup)})")
         self.sim, self.fly_name = sim, fly_name
@@ -510,9 +469,7 @@ class SensorySteering:
         if self.n_dims > 8:
             raise ValueError(f"at most 8 odor dimensions, got {self.n_dims} gains")
         self.front_edge = eye_front_edges()
-        lib = _native.lib()
-        if ctypes.sizeof(_TaxisParams) != lib.nmf_taxis_params_size():
-            raise _native.NativeError("nmf_taxis_params layout mismatch between controllers.py and libnmf_hip.so")
+        check_params(_TaxisParams, "nmf_taxis_params_size", "controllers.py")
         self._params = _TaxisParams(float(obj_threshold), float(area_threshold), float(visual_gain), float(v_min), float(v_max),
                                     float(w_ant), float(w_palp), float(odor_delta), float(base), float(drive_min), float(drive_max),
                                     (ctypes.c_int32 * 2)(*self.front_edge))

@@ -33,6 +33,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _native
+from ._handle import NativeHandle, check_params
 from .vision import Scene, body_capsules
 
 __all__ = ["HIPBatchRenderer", "CAMERA_MODES", "camera_pose", "resolve_cameras", "select_flies", "merge_flies", "FlyScene", "grid_shape",
@@ -344,7 +345,7 @@ class _Pacer:
         self.last_render_time_sec = -np.inf
 
 
-class HIPBatchRenderer(_FrameBuffer):
+class HIPBatchRenderer(NativeHandle, _FrameBuffer):
     """Renders selected worlds of a :class:`~flygym_amd.HIPSimulation` through one or several cameras, from the poses of the last
     step (``csrc/nmf_camera.hip``: one kernel launch per frame, on the stream the batch is stepped on).
 
@@ -370,6 +371,8 @@ class HIPBatchRenderer(_FrameBuffer):
     batches of such a simulation step together; pacing (:meth:`render_as_needed`) reads the step counter of the FIRST drawn
     fly's batch.
     """
+
+    _destroy_entry, _noun, _handle_attr = "nmf_camera_plan_destroy", "renderer", "_plan_h"
 
     def __init__(self, sim, cameras, *, worlds=None, camera_res=(240, 320), playback_speed: float = 0.2, output_fps: float = 25,
                  buffer_frames: bool = True, scene: Scene | None = None, ambient: float = 0.4, diffuse: float = 0.6,
@@ -423,20 +426,13 @@ class HIPBatchRenderer(_FrameBuffer):
                 v.pos[k] = pos[k]
             for k in range(9):
                 v.rot[k] = mat.reshape(9)[k]
-        p.ambient, p.diffuse, p.checker_size = self.ambient, self.diffuse, sc.checker_size
-        for i in range(3):
-            p.sky_rgb[i], p.wall_rgb[i] = sc.sky_rgb[i], sc.wall_rgb[i]
-            p.ground_rgb[0][i], p.ground_rgb[1][i] = sc.ground_rgb[0][i], sc.ground_rgb[1][i]
-            for s, c in enumerate(sc.sphere_rgb):
-                p.sphere_rgb[s][i] = c[i]
-        p.n_spheres, p.spheres_per_world, p.terrain_relief = len(sc.spheres), 0, int(sc.terrain_relief)
+        p.ambient, p.diffuse = self.ambient, self.diffuse
+        sc.fill(p)
         if several:
             self.capsule_seg, self.capsule_geom, self.capsule_rgb = merged.capsule_seg, merged.capsule_geom, merged.capsule_rgb
         else:
             self.capsule_seg, self.capsule_geom, self.capsule_rgb = (d[merged.fly_names[0]] for d in merged[3:])
-        lib = _native.lib()
-        if ctypes.sizeof(_CameraParams) != lib.nmf_camera_params_size():
-            raise _native.NativeError("nmf_camera_params layout mismatch between rendering.py and libnmf_hip.so")
+        check_params(_CameraParams, "nmf_camera_params_size", "rendering.py")
         self._params = p
         t = sim._torch
         self._spheres = t.as_tensor(sc.spheres, device=sim.device) if len(sc.spheres) else None
@@ -449,34 +445,17 @@ class HIPBatchRenderer(_FrameBuffer):
                 rec.cap_seg, rec.cap_geom, rec.cap_rgb = (merged[i][name].ctypes.data for i in (3, 4, 5))
         if several:
             cam_fly = np.asarray(merged.cam_fly, dtype=np.int32)
-            self._plan_h = lib.nmf_camera_plan_create_flies(records, len(batches), ctypes.byref(p), cam_fly.ctypes.data, len(resolved),
-                                                            ids.ctypes.data, len(ids))
+            self._create("nmf_camera_plan_create_flies", records, len(batches), ctypes.byref(p), cam_fly.ctypes.data, len(resolved),
+                         ids.ctypes.data, len(ids))
         else:
             one = records[0]
-            self._plan_h = lib.nmf_camera_plan_create(one.batch, ctypes.byref(p), len(resolved), ids.ctypes.data, len(ids),
-                                                      one.cap_seg, one.cap_geom, one.cap_rgb, one.n_caps)
-        if not self._plan_h:
-            msg = lib.nmf_last_error().decode()
-            raise ValueError(msg) if "world id" in msg else _native.NativeError(msg)
+            self._create("nmf_camera_plan_create", one.batch, ctypes.byref(p), len(resolved), ids.ctypes.data, len(ids),
+                         one.cap_seg, one.cap_geom, one.cap_rgb, one.n_caps)
         self._shape = (len(worlds), len(resolved), h, w_, 3)
 
-    # ---- lifecycle
-    def close(self) -> None:
-        if getattr(self, "_plan_h", None):
-            _native.lib().nmf_camera_plan_destroy(self._plan_h)
-            self._plan_h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+    @staticmethod
+    def _creation_error(msg: str) -> Exception:
+        return ValueError(msg) if "world id" in msg else _native.NativeError(msg)
 
     def reset(self) -> None:
         self._pacer.reset()
@@ -495,17 +474,16 @@ class HIPBatchRenderer(_FrameBuffer):
     def render_into(self, out):
         """Render into a caller-owned contiguous uint8 ``(n_selected_worlds, n_cameras, H, W, 3)`` tensor: no allocation, one
         kernel launch on the current stream — what a captured ``step(n)`` + render replays."""
-        if not self._plan_h:
-            raise RuntimeError("the renderer is closed")
+        plan = self._handle()
         t = self.sim._torch
         if tuple(out.shape) != self._shape or out.dtype != t.uint8 or out.device != self.sim.device or not out.is_contiguous():
             raise ValueError(f"render_into needs a contiguous uint8 {self._shape} tensor on {self.sim.device}")
         spheres = self._spheres.data_ptr() if self._spheres is not None else None
         lib = _native.lib()
         if self.fly_names is None:
-            _native.check(lib.nmf_camera_render(self.sim._batch_h, self._plan_h, spheres, out.data_ptr(), self.sim._stream()))
+            _native.check(lib.nmf_camera_render(self.sim._batch_h, plan, spheres, out.data_ptr(), self.sim._stream()))
         else:
-            _native.check(lib.nmf_camera_render_flies(self._plan_h, spheres, out.data_ptr(), self.sim._stream()))
+            _native.check(lib.nmf_camera_render_flies(plan, spheres, out.data_ptr(), self.sim._stream()))
         return out
 
     def render(self):

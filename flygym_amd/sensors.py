@@ -27,6 +27,8 @@ import ctypes
 import numpy as np
 
 from . import _native
+from ._handle import NativeHandle, _field_view, check_params, fly_batch, leg_segments, reset_mask, site_arrays
+from .anatomy import LEGS
 
 __all__ = ["Retina", "OdorSensors", "OdorPlume", "PathIntegrator", "RAW_IMG_HEIGHT", "RAW_IMG_WIDTH", "NUM_OMMATIDIA"]
 
@@ -161,17 +163,13 @@ class OdorSensors:
     def __init__(self, sim, fly_name: str, source_positions, peak_intensities):
         import torch
 
-        if hasattr(sim, "for_fly"):          # a world with several flies: this fly's batch
-            sim = sim.for_fly(fly_name)
-        self.sim = sim
-        fly = sim.world.fly_lookup[fly_name]
-        names = [s.name for s in fly.get_bodysegs_order()]
+        self.sim = sim = fly_batch(sim, fly_name, resolve=True)
+        seg, rel = site_arrays(sim.world.fly_lookup[fly_name], ODOR_SENSOR_SITES)
         self.source_positions = np.asarray(source_positions, dtype=np.float32).reshape(-1, 3)
         self.peak_intensities = np.asarray(peak_intensities, dtype=np.float32).reshape(len(self.source_positions), -1)
         self.n_dims = self.peak_intensities.shape[1]
         dev = sim.device
-        self._seg = torch.as_tensor(np.array([names.index(n) for n, _ in ODOR_SENSOR_SITES], dtype=np.int32), device=dev)
-        self._rel = torch.as_tensor(np.array([r for _, r in ODOR_SENSOR_SITES], dtype=np.float32), device=dev)
+        self._seg, self._rel = torch.as_tensor(seg, device=dev), torch.as_tensor(rel, device=dev)
         self._pos = torch.as_tensor(self.source_positions, device=dev)
         self._peak = torch.as_tensor(self.peak_intensities, device=dev)
 
@@ -196,7 +194,7 @@ class _PlumeParams(ctypes.Structure):
                 ("intensity_scale", ctypes.c_float), ("seed", ctypes.c_uint32)]
 
 
-class OdorPlume:
+class OdorPlume(NativeHandle):
     """Time-varying odor plumes on the GPU, one per world, and the fly's four odor sensors in them (``nmf_plume_*``).
 
     A plume is a float32 concentration grid over the ground plane (cell ``(j, i)`` centred at ``origin + ((i + 1/2), (j + 1/2)) *
@@ -226,16 +224,14 @@ class OdorPlume:
     word back; :meth:`advance` and the readings can be captured in a graph and replayed.
     """
 
+    _destroy_entry, _noun, _views = "nmf_plume_destroy", "plume", ("wind", "ticks", "buffers", "parity")
+
     def __init__(self, sim, fly_name: str, *, grid, cell_size: float, origin=(0.0, 0.0), source, mean_wind=(0.0, 0.0),
                  wind_tau: float = 1.0, wind_sigma: float = 0.0, diffusivity: float = 0.0, tick_s: float = 0.01, eddies=None,
                  eddy_gain: float = 1.0, intensity_scale: float = 1.0, per_world: bool = True, seed: int = 0, first_world: int = 0):
-        from .simulation import _tensor_from_ptr
-
-        if hasattr(sim, "for_fly"):          # a world with several flies: this fly's batch
-            sim = sim.for_fly(fly_name)
+        sim = fly_batch(sim, fly_name, resolve=True)
         self.sim, self.fly_name = sim, fly_name
-        fly = sim.world.fly_lookup[fly_name]
-        names = [s.name for s in fly.get_bodysegs_order()]
+        seg, rel = site_arrays(sim.world.fly_lookup[fly_name], ODOR_SENSOR_SITES)
         H, W = (int(v) for v in grid)
         self.grid, self.cell_size, self.origin = (H, W), float(cell_size), (float(origin[0]), float(origin[1]))
         self.n_worlds, self.tick_s = int(sim.n_worlds), float(tick_s)
@@ -251,31 +247,18 @@ class OdorPlume:
             self.eddies = np.ascontiguousarray(eddies, dtype=np.float32)
             if self.eddies.shape != (H, W, 2):
                 raise ValueError(f"eddies must have shape {(H, W, 2)}, got {self.eddies.shape}")
-        lib = _native.lib()
-        if ctypes.sizeof(_PlumeParams) != lib.nmf_plume_params_size():
-            raise _native.NativeError("nmf_plume_params layout mismatch between sensors.py and libnmf_hip.so")
+        check_params(_PlumeParams, "nmf_plume_params_size", "sensors.py")
         self._params = _PlumeParams(self.n_plumes, H, W, int(first_world), self.cell_size, self.origin[0], self.origin[1], self.tick_s,
                                     float(diffusivity), float(mean_wind[0]), float(mean_wind[1]), float(wind_tau), float(wind_sigma),
                                     float(eddy_gain), float(intensity_scale), int(seed) & 0xFFFFFFFF)
-        self._h = lib.nmf_plume_create(sim._batch_h, ctypes.byref(self._params), self.source.ctypes.data,
-                                       None if self.eddies is None else self.eddies.ctypes.data)
-        if not self._h:
-            raise _native.NativeError(lib.nmf_last_error().decode())
-        t = sim._torch
-        dev = sim.device
-
-        def view(which, shape, typestr="<f4"):
-            ptr = lib.nmf_plume_field_ptr(self._h, which, None)
-            if not ptr:
-                raise _native.NativeError(lib.nmf_last_error().decode())
-            return _tensor_from_ptr(t, ptr, shape, dev, typestr)
-
-        self.wind = view(0, (self.n_plumes, 2))
-        self.ticks = view(1, (self.n_plumes,), "<i4")
-        self.buffers = (view(2, (self.n_plumes, H, W)), view(3, (self.n_plumes, H, W)))
-        self.parity = view(4, (1,), "<i4")
-        self._seg = t.as_tensor(np.array([names.index(n) for n, _ in ODOR_SENSOR_SITES], dtype=np.int32), device=dev)
-        self._rel = t.as_tensor(np.array([r for _, r in ODOR_SENSOR_SITES], dtype=np.float32), device=dev)
+        h = self._create("nmf_plume_create", sim._batch_h, ctypes.byref(self._params), self.source.ctypes.data,
+                         None if self.eddies is None else self.eddies.ctypes.data)
+        t, dev, field_ptr = sim._torch, sim.device, _native.lib().nmf_plume_field_ptr
+        self.wind = _field_view(sim, field_ptr, h, 0, "<f4", (self.n_plumes, 2))
+        self.ticks = _field_view(sim, field_ptr, h, 1, "<i4", (self.n_plumes,))
+        self.buffers = tuple(_field_view(sim, field_ptr, h, which, "<f4", (self.n_plumes, H, W)) for which in (2, 3))
+        self.parity = _field_view(sim, field_ptr, h, 4, "<i4", (1,))
+        self._seg, self._rel = t.as_tensor(seg, device=dev), t.as_tensor(rel, device=dev)
         self.out_of_bounds = t.zeros((self.n_worlds,), dtype=t.uint8, device=dev)
 
     @staticmethod
@@ -287,30 +270,6 @@ class OdorPlume:
         inside = (xc[None, :] - x) ** 2 + (yc[:, None] - y) ** 2 <= radius ** 2
         return np.where(inside, np.float32(peak), np.float32(0)).astype(np.float32)
 
-    # ---- lifecycle
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _native.lib().nmf_plume_destroy(self._h)
-            self._h = None
-            self.wind = self.ticks = self.buffers = self.parity = None        # (views of freed memory)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _handle(self):
-        if not getattr(self, "_h", None):
-            raise RuntimeError("the plume is closed")
-        return self._h
-
     # ---- the field
     def advance(self, n_ticks: int = 1) -> None:
         """``n_ticks`` plume ticks of every plume (two launches per tick; no host sync)."""
@@ -320,13 +279,7 @@ class OdorPlume:
         """The plumes of ``mask`` (``(n_plumes,)`` bool, numpy or torch; default all) get empty grids, tick 0 and the mean wind;
         the others keep their state."""
         h = self._handle()
-        t = self.sim._torch
-        m = None
-        if mask is not None:
-            m = t.as_tensor(mask, device=self.sim.device)
-            if tuple(m.shape) != (self.n_plumes,):
-                raise ValueError(f"Expected a reset mask of shape ({self.n_plumes},), but got {tuple(m.shape)}")
-            m = (m != 0).to(t.uint8).contiguous()
+        m = reset_mask(mask, self.n_plumes, self.sim)
         _native.check(_native.lib().nmf_plume_reset(h, None if m is None else m.data_ptr(), self.sim._stream()))
 
     def set_wind(self, wind) -> None:
@@ -381,7 +334,7 @@ class _OdometryParams(ctypes.Structure):
                 ("contact_force_threshold", ctypes.c_float * 6)]
 
 
-class PathIntegrator:
+class PathIntegrator(NativeHandle):
     """Path integration on the GPU (``nmf_odometry_*``): the fly's heading and position estimated from proprioception alone, from
     how far each leg's tip travels relative to the body while the leg is on the ground.
 
@@ -414,22 +367,18 @@ class PathIntegrator:
     launch and can be captured in a graph after the tick's last step.  Close the integrator before its simulation.
     """
 
-    def __init__(self, sim, fly_name: str, *, window: int, contact_force_thresholds=(0.0, 0.0, 0.0), coefficients=None):
-        from .anatomy import LEGS
-        from .simulation import _field_view, _tensor_from_ptr
+    _destroy_entry, _noun = "nmf_odometry_destroy", "integrator"
+    _views = ("stride_total", "window_strides", "heading", "position", "home", "count", "coefficients")
 
-        if hasattr(sim, "for_fly"):
-            raise ValueError(f"a world with several flies has one batch per fly: pass sim.for_fly({fly_name!r})")
+    def __init__(self, sim, fly_name: str, *, window: int, contact_force_thresholds=(0.0, 0.0, 0.0), coefficients=None):
+        sim = fly_batch(sim, fly_name, resolve=False)
         if fly_name not in sim.world.fly_lookup:
             raise ValueError(f"no fly named {fly_name!r} in this simulation ({', '.join(sim.world.fly_lookup)})")
         if len(contact_force_thresholds) != 3:
             raise ValueError(f"contact_force_thresholds takes one value for each of 'f', 'm', 'h', got {contact_force_thresholds!r}")
         self.sim, self.fly_name = sim, fly_name
         self.n_worlds, self.window = int(sim.n_worlds), int(window)
-        fly = sim.world.fly_lookup[fly_name]
-        segs = [s.name for s in fly.get_bodysegs_order()]
-        self.root_seg = segs.index(fly.root_segment.name)
-        self.tip_seg = np.array([segs.index(f"{leg}_tarsus5") for leg in LEGS], dtype=np.int32)
+        self.root_seg, self.tip_seg = leg_segments(sim.world.fly_lookup[fly_name], LEGS)
         by_pos = dict(zip("fmh", (float(v) for v in contact_force_thresholds)))
         self.contact_force_thresholds = np.array([by_pos[leg[1]] for leg in LEGS], dtype=np.float32)
         coef = None
@@ -437,44 +386,15 @@ class PathIntegrator:
             coef = np.ascontiguousarray(coefficients, dtype=np.float64).reshape(-1)
             if coef.size != 14:
                 raise ValueError(f"coefficients takes 14 values (heading_coef[6], disp_coef[6], heading_bias, disp_bias), got {coef.size}")
-        lib = _native.lib()
-        if ctypes.sizeof(_OdometryParams) != lib.nmf_odometry_params_size():
-            raise _native.NativeError("nmf_odometry_params layout mismatch between sensors.py and libnmf_hip.so")
+        check_params(_OdometryParams, "nmf_odometry_params_size", "sensors.py")
         self._params = _OdometryParams(self.window, self.root_seg, (ctypes.c_int32 * 6)(*self.tip_seg.tolist()),
                                        (ctypes.c_float * 6)(*self.contact_force_thresholds.tolist()))
-        self._h = lib.nmf_odometry_create(sim._batch_h, ctypes.byref(self._params), None if coef is None else coef.ctypes.data)
-        if not self._h:
-            raise _native.NativeError(lib.nmf_last_error().decode())
-        view = lambda which, typestr="<f8": _field_view(sim, lib.nmf_odometry_field_ptr, self._h, which, typestr)
+        h = self._create("nmf_odometry_create", sim._batch_h, ctypes.byref(self._params), None if coef is None else coef.ctypes.data)
+        view = lambda which, typestr="<f8", shape=None: _field_view(sim, _native.lib().nmf_odometry_field_ptr, h, which, typestr, shape)
         self.stride_total, self.window_strides = view(0), view(1)
         self.heading, self.position, self.home = view(2).reshape(self.n_worlds), view(3), view(4)
         self.count = view(5, "<i4").reshape(self.n_worlds)
-        self.coefficients = _tensor_from_ptr(sim._torch, lib.nmf_odometry_field_ptr(self._h, 6, None), (14,), sim.device, "<f8")
-
-    # ---- lifecycle
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _native.lib().nmf_odometry_destroy(self._h)
-            self._h = None
-            self.stride_total = self.window_strides = self.heading = self.position = self.home = None      # (views of freed memory)
-            self.count = self.coefficients = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _handle(self):
-        if not getattr(self, "_h", None):
-            raise RuntimeError("the integrator is closed")
-        return self._h
+        self.coefficients = view(6, shape=(14,))
 
     # ---- the estimate
     def update(self) -> None:
@@ -487,12 +407,7 @@ class PathIntegrator:
         not read); the others keep their state."""
         h = self._handle()
         t = self.sim._torch
-        m = p = None
-        if mask is not None:
-            m = t.as_tensor(mask, device=self.sim.device)
-            if tuple(m.shape) != (self.n_worlds,):
-                raise ValueError(f"Expected a reset mask of shape ({self.n_worlds},), but got {tuple(m.shape)}")
-            m = (m != 0).to(t.uint8).contiguous()
+        m, p = reset_mask(mask, self.n_worlds, self.sim), None
         if pose is not None:
             p = t.as_tensor(pose)
             if tuple(p.shape) != (self.n_worlds, 3):

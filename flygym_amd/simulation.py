@@ -16,6 +16,7 @@ import warnings
 import numpy as np
 
 from . import _native
+from ._handle import _field_view, reset_mask
 from .compose.fly import ActuatorType
 from .compose.world import BaseWorld
 
@@ -202,12 +203,8 @@ class HIPSimulation:
     def reset_worlds(self, mask) -> None:
         """Reset only the worlds where ``mask`` (``(n_worlds,)`` bool, numpy or torch) is set: keyframe pose, zero
         velocity, clock at 0.  The other worlds keep their state.  Stream-ordered device work (no host sync)."""
-        t = self._torch
-        m = t.as_tensor(mask, device=self.device)
-        if tuple(m.shape) != (self.n_worlds,):
-            raise ValueError(f"Expected a reset mask of shape ({self.n_worlds},), but got {tuple(m.shape)}")
-        m = (m != 0).to(t.uint8).contiguous()
-        _native.check(self._lib.nmf_reset_worlds(self._batch_h, m.data_ptr(), self._stream()))
+        m = reset_mask(mask, self.n_worlds, self)
+        _native.check(self._lib.nmf_reset_worlds(self._batch_h, None if m is None else m.data_ptr(), self._stream()))
 
     def step(self, n_steps: int = 1, record_every: int | None = None, n_act: int = 42):
         """Advance all worlds by one timestep (``n_steps`` > 1 fuses several into one launch).
@@ -611,31 +608,6 @@ class MultiFlyHIPSimulation(HIPSimulation):
 
     @property
     def mj_data(self): self._one_batch_only("mj_data")
-
-
-def _tensor_from_ptr(torch, ptr: int, shape, device, typestr: str = "<f4"):
-    """Wrap a raw device pointer as a torch tensor without copying."""
-    n = int(np.prod(shape))
-
-    class _Holder:
-        pass
-
-    h = _Holder()
-    h.__cuda_array_interface__ = {
-        "shape": (max(n, 1),), "typestr": typestr, "data": (int(ptr), False), "version": 3, "strides": None,
-    }
-    t = torch.as_tensor(h, device=device)
-    return t[:n].reshape(shape)
-
-
-def _field_view(sim, field_ptr, handle, which: int, typestr: str = "<f4"):
-    """Zero-copy view ``(n_worlds, width)`` of field ``which`` of a native handle on ``sim``'s device; ``field_ptr`` is the handle's
-    ``nmf_*_field_ptr`` entry point."""
-    width = ctypes.c_int32(0)
-    ptr = field_ptr(handle, which, ctypes.byref(width))
-    if not ptr:
-        raise _native.NativeError(_native.lib().nmf_last_error().decode())
-    return _tensor_from_ptr(sim._torch, ptr, (sim.n_worlds, max(width.value, 0)), sim.device, typestr)
 
 
 class _DataView:

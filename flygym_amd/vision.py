@@ -30,6 +30,7 @@ import ctypes
 import numpy as np
 
 from . import _native
+from ._handle import NativeHandle, check_params, fly_batch
 from .sensors import EYE_CAMERAS, FOVY_PER_EYE_DEG, Retina
 
 __all__ = ["EyeRenderer", "Scene"]
@@ -108,9 +109,23 @@ class Scene:
         if len(self.spheres) != len(self.sphere_rgb) or len(self.spheres) > 8:
             raise ValueError("need one colour per sphere and at most 8 spheres")
 
+    def fill(self, p) -> None:
+        """Set the scene fields that ``nmf_eye_params`` and ``nmf_camera_params`` share (``fill_scene`` of csrc/nmf_capi.hip reads
+        them back): the colours, the checker, ``n_spheres`` (spheres shared by all worlds) and ``terrain_relief``."""
+        p.checker_size = self.checker_size
+        for i in range(3):
+            p.sky_rgb[i], p.wall_rgb[i] = self.sky_rgb[i], self.wall_rgb[i]
+            p.ground_rgb[0][i], p.ground_rgb[1][i] = self.ground_rgb[0][i], self.ground_rgb[1][i]
+            for s, c in enumerate(self.sphere_rgb):
+                p.sphere_rgb[s][i] = c[i]
+        p.n_spheres, p.spheres_per_world, p.terrain_relief = len(self.spheres), 0, int(self.terrain_relief)
 
-class EyeRenderer:
-    """Renders both compound eyes of every fly in a ``HIPSimulation`` from the poses of the last step."""
+
+class EyeRenderer(NativeHandle):
+    """Renders both compound eyes of every fly in a ``HIPSimulation`` from the poses of the last step.  It owns a visit plan of
+    the library: :meth:`close` (or the ``with`` form) frees it, and the ``render*`` methods then raise ``RuntimeError``."""
+
+    _destroy_entry, _noun, _handle_attr = "nmf_eye_plan_destroy", "renderer", "_plan_h"
 
     def __init__(self, sim, fly_name: str, scene: Scene | None = None, retina: Retina | None = None,
                  fov_deg: float = FOVY_PER_EYE_DEG, rays_per_ommatidium: int = 0):
@@ -123,8 +138,7 @@ class EyeRenderer:
         if rays_per_ommatidium not in (0, 16):
             raise ValueError("rays_per_ommatidium must be 0 (every pixel) or 16")
 
-        if hasattr(sim, "for_fly"):          # a world with several flies: this fly's batch
-            sim = sim.for_fly(fly_name)
+        sim = fly_batch(sim, fly_name, resolve=True)
         self.sim, self.scene, self.retina = sim, scene or Scene(), retina or Retina()
         fly = sim.world.fly_lookup[fly_name]
         names = [s.name for s in fly.get_bodysegs_order()]
@@ -139,22 +153,15 @@ class EyeRenderer:
             for i in range(4):
                 p.rel_quat[e][i] = quat[i]
             self.cameras.append((seg, np.asarray(pos, dtype=np.float64), quat))
-        p.checker_size = self.scene.checker_size
+        self.scene.fill(p)
         for i in range(3):
-            p.sky_rgb[i] = self.scene.sky_rgb[i]
-            p.ground_rgb[0][i], p.ground_rgb[1][i] = self.scene.ground_rgb[0][i], self.scene.ground_rgb[1][i]
-            p.wall_rgb[i], p.body_rgb[i] = self.scene.wall_rgb[i], self.scene.body_rgb[i]
-            for s, c in enumerate(self.scene.sphere_rgb):
-                p.sphere_rgb[s][i] = c[i]
-        p.n_spheres, p.spheres_per_world = len(self.scene.spheres), 0
-        p.terrain_relief = int(self.scene.terrain_relief)
+            p.body_rgb[i] = self.scene.body_rgb[i]
         p.rays_per_ommatidium = int(rays_per_ommatidium)
         self.capsule_seg, self.capsule_geom = body_capsules(fly) if self.scene.own_body else (np.zeros(0, np.int32), np.zeros((0, 7), np.float32))
         p.n_capsules = len(self.capsule_seg)
         self._cap_seg = torch.as_tensor(self.capsule_seg, device=sim.device) if p.n_capsules else None
         self._cap_geom = torch.as_tensor(self.capsule_geom, device=sim.device) if p.n_capsules else None
-        if ctypes.sizeof(_EyeParams) != _native.lib().nmf_eye_params_size():
-            raise _native.NativeError("nmf_eye_params layout mismatch between vision.py and libnmf_hip.so")
+        check_params(_EyeParams, "nmf_eye_params_size", "vision.py")
         self._params = p
         self._spheres = torch.as_tensor(self.scene.spheres, device=sim.device) if len(self.scene.spheres) else None
         # the visit plan: an explicit handle of the library (nmf_eye_plan_create — synchronous, once), so that every render call is
@@ -163,18 +170,8 @@ class EyeRenderer:
         if plan is None:
             raise ValueError("the eye renderer needs a retina whose pixel count is a multiple of 16")
         torch.cuda.synchronize(sim.device)
-        self._plan_h = _native.lib().nmf_eye_plan_create(id_map.data_ptr(), plan.data_ptr(), pale.data_ptr(), inv_norm.data_ptr(),
-                                                         p.height, p.width, p.fov_deg, self.retina.num_ommatidia, sim.device_index)
-        if not self._plan_h:
-            raise _native.NativeError(_native.lib().nmf_last_error().decode())
-
-    def __del__(self):
-        try:
-            if getattr(self, "_plan_h", None):
-                _native.lib().nmf_eye_plan_destroy(self._plan_h)
-                self._plan_h = None
-        except Exception:
-            pass
+        self._create("nmf_eye_plan_create", id_map.data_ptr(), plan.data_ptr(), pale.data_ptr(), inv_norm.data_ptr(),
+                     p.height, p.width, p.fov_deg, self.retina.num_ommatidia, sim.device_index)
 
     def set_spheres(self, spheres) -> None:
         """Move the spheres: ``(n_spheres, 4)`` shared by all worlds or ``(n_worlds, n_spheres, 4)`` per world
@@ -192,7 +189,7 @@ class EyeRenderer:
 
     def _call(self, frames, omm):
         _native.check(_native.lib().nmf_eye_render_planned(
-            self.sim._batch_h, ctypes.byref(self._params), self._plan_h,
+            self.sim._batch_h, ctypes.byref(self._params), self._handle(),
             self._spheres.data_ptr() if self._spheres is not None else None,
             self._cap_seg.data_ptr() if self._cap_seg is not None else None,
             self._cap_geom.data_ptr() if self._cap_geom is not None else None,
