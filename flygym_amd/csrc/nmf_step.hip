@@ -198,7 +198,13 @@ __global__ void __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(wave
       const int my_ctrl = tab && lane < rp.n_act ? rp.act_ids[ln] : -1;
       CtrlPrefetch pf;
       pf.mine = my_ctrl >= 0; pf.next_row = nullptr;
-      pf.value = my_ctrl >= 0 ? tab[(size_t)((rp.start + step0) % rp.table_steps) * rp.n_act + lane] : 0.f;     // the item's first row travels with the state
+      // the control row of the current step: the one modulo of the item; the step loop advances it a row at a time and
+      // wraps it by a compare (kStepCursor, nmf_step_lds.h; the step loop's own modulos are the old form)
+      int row = 0;
+      if constexpr (kStepCursor<TP>) {
+        if (tab) row = (rp.start + step0) % rp.table_steps;
+        pf.value = my_ctrl >= 0 ? tab[(size_t)row * rp.n_act + lane] : 0.f;     // the item's first row travels with the state
+      } else pf.value = my_ctrl >= 0 ? tab[(size_t)((rp.start + step0) % rp.table_steps) * rp.n_act + lane] : 0.f;
       if (chunk > 0) {
         // the world's previous chunk (an older ticket: its item is running or done) leaves the state as tagged granules
         const unsigned int want = (unsigned int)__builtin_amdgcn_readfirstlane((int)(epoch * 32u + (unsigned int)chunk));
@@ -230,13 +236,23 @@ __global__ void __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(wave
       for (int step = step0; step < step1; ++step) {
         if (tab) {
           if (my_ctrl >= 0) s.ctrl[my_ctrl] = pf.value;
-          const float* src = tab + (size_t)((rp.start + step) % rp.table_steps) * rp.n_act;
-          for (int a = opaque(lane) + kWave; a < rp.n_act; a += kWave) s.ctrl[rp.act_ids[a]] = src[a];     // (more than 64 controls: hybrid / tree kernels)
-          pf.next_row = step + 1 < step1 ? tab + (size_t)((rp.start + step + 1) % rp.table_steps) * rp.n_act : nullptr;
+          if constexpr (kStepCursor<TP>) {
+            if constexpr (TP::kCtrl > kWave) {     // (more than 64 controls: the 96-control hybrid and the tree kernels)
+              const float* src = tab + (size_t)row * rp.n_act;
+              for (int a = opaque(lane) + kWave; a < rp.n_act; a += kWave) s.ctrl[rp.act_ids[a]] = src[a];
+            }
+            row = row + 1 == rp.table_steps ? 0 : row + 1;
+            pf.next_row = step + 1 < step1 ? tab + (size_t)row * rp.n_act : nullptr;
+          } else {
+            const float* src = tab + (size_t)((rp.start + step) % rp.table_steps) * rp.n_act;
+            for (int a = opaque(lane) + kWave; a < rp.n_act; a += kWave) s.ctrl[rp.act_ids[a]] = src[a];     // (more than 64 controls: hybrid / tree kernels)
+            pf.next_row = step + 1 < step1 ? tab + (size_t)((rp.start + step + 1) % rp.table_steps) * rp.n_act : nullptr;
+          }
           WSYNC();
         }
         STAGE(0);
-        // an observation ring records this step: its row (wave-uniform address)
+        // an observation ring records this step: its row (wave-uniform address).  (Launches without a ring never reach the
+        // modulo; a countdown carried across the loop in its place cost every leg-chain kernel a spilled register: dropped)
         float* rec = nullptr;
         if (st.obs_every > 0 && (step + 1) % st.obs_every == 0)
           rec = st.ring + ((size_t)((step + 1) / st.obs_every - 1) * (size_t)st.n_worlds + (size_t)w) * (size_t)st.ring_stride;

@@ -22,7 +22,7 @@ __device__ bool physics_forward(FlyLds<TP>& s, const GModel& m, int lane, const 
   if constexpr (TP::kStar) { if constexpr (TP::REST_B > 0) { if (lane == 0) s.reduced = 0; } }
   stage_kinematics(s, m, lane);
   STAGE(1);
-  stage_inertia(s, m, lane);
+  if constexpr (!kInertiaInKin<TP>) stage_inertia(s, m, lane);      // (leg-chain kernels: inside stage_kinematics)
   STAGE(2);
   stage_collision<TP, TP::kTerrain>(s, m, lane);
   if (pf.next_row && pf.mine) pf.value = G(pf.next_row)[lane];      // consumed at the top of the next step

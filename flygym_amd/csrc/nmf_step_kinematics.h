@@ -1,7 +1,8 @@
 // nmf_step_kinematics.h — kinematics and inertia stages.  stage_kinematics reads qpos and leaves the body poses (xmat / xpos:
 // overlaid on the solver vectors and the contact wrenches, alive until the end of the collision stage) and the motion subspaces
 // S; its scratch is qacc_smooth..vD (joint quaternions), T..W (relative transforms) and Ib (body-frame axes).  stage_inertia
-// then rebuilds Ib (and Isym) about the root origin from the poses.
+// then rebuilds Ib (and Isym) about the root origin from the poses — in the leg-chain kernels stage_kinematics does so itself,
+// last, from constants it requested at its entry (kInertiaInKin, nmf_step_lds.h).
 //
 // Not self-contained: one of the stage headers that nmf_step.hip includes in stage order to form the stepping kernel's
 // translation unit, and it relies on the ones before it.
@@ -9,6 +10,50 @@
 #include "nmf_device.h"
 
 namespace nmf {
+
+// ------------------------------------------------------------------ inertia of one body
+// A body's inertial constants of the model, as stage_kinematics holds them from its entry on (kInertiaInKin): the body-frame
+// inertia (xx, yy, zz, xy, xz, yz), the centre of mass and the mass
+struct BodyInertial { float q[6], ipos[3], mass; };
+__device__ __forceinline__ BodyInertial ld_inertial(const GModel& m, int b) {
+  BodyInertial k;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) k.q[i] = m.body_inertia[6 * b + i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) k.ipos[i] = m.body_ipos[3 * b + i];
+  k.mass = m.body_mass[b];
+  return k;
+}
+// Ib (and Isym) of body b about the root origin from its pose and its constants in registers: stage_inertia's expressions
+template <class TP>
+__device__ __forceinline__ void inertia_of_body(FlyLds<TP>& s, int b, const float* q, const float* ipos, const float* mass) {
+  {
+    const float* R = s.xmat()[b];
+    float Il[9] = {q[0], q[3], q[4], q[3], q[1], q[5], q[4], q[5], q[2]};
+    float Tm[9], Iw[9];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) Tm[3 * i + j] = R[3 * i] * Il[j] + R[3 * i + 1] * Il[3 + j] + R[3 * i + 2] * Il[6 + j];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) Iw[3 * i + j] = Tm[3 * i] * R[3 * j] + Tm[3 * i + 1] * R[3 * j + 1] + Tm[3 * i + 2] * R[3 * j + 2];
+    V3 c = mat_vec(R, ld3(ipos)) + (ld3(s.xpos()[b]) - ld3(s.xpos()[0]));
+    float ms = *mass, cc = dot(c, c);
+    float* I = s.Ib[b];
+    I[0] = ms; I[1] = ms * c.x; I[2] = ms * c.y; I[3] = ms * c.z;
+    I[4] = Iw[0] + ms * (cc - c.x * c.x); I[5] = Iw[4] + ms * (cc - c.y * c.y); I[6] = Iw[8] + ms * (cc - c.z * c.z);
+    I[7] = Iw[1] - ms * c.x * c.y; I[8] = Iw[2] - ms * c.x * c.z; I[9] = Iw[5] - ms * c.y * c.z;
+    if constexpr (kHasIsym<TP>) {
+      float* Q = s.Isym[b];                // [[I, [h]x], [-[h]x, m 1]], upper triangle row-major
+      Q[0] = I[4]; Q[1] = I[7]; Q[2] = I[8]; Q[3] = 0.f;   Q[4] = -I[3]; Q[5] = I[2];
+      Q[6] = I[5]; Q[7] = I[9]; Q[8] = I[3]; Q[9] = 0.f;   Q[10] = -I[1];
+      Q[11] = I[6]; Q[12] = -I[2]; Q[13] = I[1]; Q[14] = 0.f;
+      Q[15] = ms; Q[16] = 0.f; Q[17] = 0.f; Q[18] = ms; Q[19] = 0.f; Q[20] = ms;
+    }
+  }
+}
 
 // ------------------------------------------------------------------ kinematics
 template <class TP>
@@ -26,6 +71,14 @@ __device__ __noinline__ void stage_kinematics(FlyLds<TP>& s, const GModel& m, in
   const HotModel hmk = hot_model(s, m);
   const gptr<float> g_axis = G(hmk.dof_axis), g_quat = G(hmk.body_quat), g_pos = G(hmk.body_pos);
   auto axis_of = [&](int j) { if constexpr (kHasIsym<TP>) return ld3(s.axis[j]); else return ld3(g_axis + 3 * j); };
+  // kInertiaInKin: lane b's inertial constants are requested here and used behind the motion subspaces, a stage's length later
+  // (requested behind the caller's return instead, the call's drained memory counter put their round trip in front of the
+  // inertia stage's first line)
+  BodyInertial inertial;
+  if constexpr (kInertiaInKin<TP>) {
+    static_assert(!kInertiaInKin<TP> || TP::NB <= kWave, "one body per lane");
+    if (lane < s.nb()) inertial = ld_inertial(m, lane);
+  }
   for (int j = 6 + lane; j < s.nv(); j += kWave) {
     float sn, cs;
     sincos_bounded(0.5f * s.qpos[j + 1], &sn, &cs);
@@ -113,8 +166,14 @@ __device__ __noinline__ void stage_kinematics(FlyLds<TP>& s, const GModel& m, in
     stsv(s.S[j], S);
   }
   WSYNC();
+  if constexpr (kInertiaInKin<TP>) {     // the pass above read the body-frame axes that lie in Ib: only now is it rebuilt
+    if (lane < s.nb()) inertia_of_body(s, lane, inertial.q, inertial.ipos, &inertial.mass);
+    WSYNC();
+  }
 }
 
+// The inertia stage of the kernels whose stage_kinematics does not build Ib itself (kInertiaInKin).  The expressions are those of
+// inertia_of_body; they stay spelled out here so that these kernels (256 VGPRs, a spill apart) compile to what they were.
 template <class TP>
 __device__ void stage_inertia(FlyLds<TP>& s, const GModel& m, int lane) {
   for (int b = lane; b < s.nb(); b += kWave) {

@@ -152,6 +152,30 @@ template <class TP> constexpr bool euler_fused() {
 #endif
 }
 template <class TP> inline constexpr bool kEulerFused = euler_fused<TP>();
+// The fixed cost of a step around its stages (DESIGN_APPENDIX.md section N): the step loop of nmf_step_kernel carries the
+// control table's row from step to step and wraps it by a compare instead of taking two run-time modulos per step, and the
+// loop for controls 64 and up exists only in kernels that can hold as many.  The hybrid terrain kernels keep the old loop: the
+// cursor cost the ALL_BIOLOGICAL one a spilled register.  And in the leg-chain kernels of flat and tethered worlds
+// stage_kinematics requests the bodies' inertial constants at its entry and builds Ib / Isym itself, last (kInertiaInKin): the
+// model's round trip runs under the stage instead of behind the call's return, in front of the inertia stage's first line.
+// (Their terrain kernels keep the inertia stage: with the move the blocks bench lost 0.4 %.)
+// -DNMF_STEP_FIXED_OLD: the old loop and the inertia stage everywhere — the machine code from before the change.
+template <class TP> constexpr bool step_cursor() {
+#ifdef NMF_STEP_FIXED_OLD
+  return false;
+#else
+  if constexpr (TP::kStar) return !(TP::REST_B > 0 && TP::kTerrain); else return true;
+#endif
+}
+template <class TP> constexpr bool inertia_in_kinematics() {
+#ifdef NMF_STEP_FIXED_OLD
+  return false;
+#else
+  return has_cm3<TP>() && !TP::kTerrain;
+#endif
+}
+template <class TP> inline constexpr bool kStepCursor = step_cursor<TP>();
+template <class TP> inline constexpr bool kInertiaInKin = inertia_in_kinematics<TP>();
 // Leg-chain kernels: the rank-1 downdates of the fused smooth solve's two chains (legs and root) run on the matrix pipe
 // (grp8_rank1_mfma, nmf_device.h) instead of six group broadcasts through the LDS crossbar and three v_pk_fma_f32 each — the
 // same multiply-adds, the same bits.  -DNMF_ABA_RANK1_VALU: the broadcasts and packed multiply-adds everywhere, as before.
