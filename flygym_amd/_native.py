@@ -190,6 +190,12 @@ def lib():
             "nmf_odometry_reset": (ci, [vp, vp, vp, vp]),
             "nmf_odometry_update": (ci, [vp, vp]),
             "nmf_odometry_field_ptr": (vp, [vp, ci, ctypes.POINTER(ctypes.c_int32)]),
+            "nmf_motion_params_size": (ctypes.c_size_t, []),
+            "nmf_motion_create": (vp, [vp, vp, vp, vp, ci, ci]),
+            "nmf_motion_destroy": (None, [vp]),
+            "nmf_motion_reset": (ci, [vp, vp, vp]),
+            "nmf_motion_update": (ci, [vp, vp, vp, vp, vp]),
+            "nmf_motion_field_ptr": (vp, [vp, ci, ctypes.POINTER(ctypes.c_int32)]),
             "nmf_odor_intensity": (ci, [vp, vp, vp, ci, vp, vp, ci, ci, vp, vp]),
             "nmf_replay_resample": (ci, [vp, ci, ci, ctypes.c_double, ctypes.c_double, vp, ci, ci, vp, vp]),
         }

@@ -20,9 +20,9 @@
 #include "nmf_step.hip"
 #include "nmf_sensors.hip"
 // `#pragma clang fp reassociate(off)` at file scope holds from the first file that sets it to the end of the translation unit:
-// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip, nmf_plume.hip, nmf_taxis.hip, nmf_odometry.hip and the host code
+// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip, nmf_plume.hip, nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip and the host code
 // below are all compiled under it, and the files above are not.  Which files it covers decides their kernels' arithmetic: keep the
-// order (nmf_taxis.hip and nmf_odometry.hip add pragmas inside their functions only: nothing of them reaches past the file).
+// order (nmf_taxis.hip, nmf_odometry.hip and nmf_motion.hip add pragmas inside their functions only: nothing of them reaches past the file).
 #include "nmf_eyes.hip"
 #include "nmf_camera.hip"
 #include "nmf_replay.hip"
@@ -30,6 +30,7 @@
 #include "nmf_plume.hip"
 #include "nmf_taxis.hip"
 #include "nmf_odometry.hip"
+#include "nmf_motion.hip"
 #include "nmf_skeleton.h"      // nmf_model, the blob parser, classify_skeleton
 #endif
 
@@ -62,7 +63,7 @@ struct DeviceGuard {
   DeviceGuard guard_((b)->mem.device);                                                        \
   if (guard_.err != hipSuccess) return fail(std::string("hipSetDevice: ") + hipGetErrorString(guard_.err))
 
-// The device memory of one handle (batch, eye plan, camera plan, CPG, plume, odometry): every allocation is 16-byte granular, recorded, and freed
+// The device memory of one handle (batch, eye plan, camera plan, CPG, plume, odometry, motion): every allocation is 16-byte granular, recorded, and freed
 // with the handle.  The first failure sets the error text, named after the entry point `who`, and sticks: later calls return
 // null without touching the device, so that a caller tests `ok` once after its last allocation.
 struct DevMem {
@@ -1638,6 +1639,105 @@ extern "C" int nmf_odometry_update(nmf_odometry* O, void* stream) {
   DEVICE_GUARD(O);
   hipLaunchKernelGGL(nmf::nmf_odometry_update_kernel, dim3((unsigned)((O->n_worlds + nmf::kOdoWorlds - 1) / nmf::kOdoWorlds)), dim3(nmf::kOdoThreads),
                      0, (hipStream_t)stream, O->args, O->ptrs);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// ---- motion vision (nmf_motion.hip) ----
+// The shared pair list, the per-world filter state and the outputs.
+struct nmf_motion {
+  int n_worlds = 0;
+  nmf::MotionArgs args{};
+  nmf::MotionPtrs ptrs{};
+  float* drive = nullptr;
+  DevMem mem;
+};
+
+extern "C" size_t nmf_motion_params_size(void) { return sizeof(nmf_motion_params); }
+
+extern "C" void nmf_motion_destroy(nmf_motion* M) {
+  if (!M) return;
+  M->mem.release();
+  delete M;
+}
+
+extern "C" int nmf_motion_reset(nmf_motion* M, const uint8_t* mask_dev, void* stream) {
+  if (!M) return fail("nmf_motion_reset: null handle");
+  DEVICE_GUARD(M);
+  hipLaunchKernelGGL(nmf::nmf_motion_reset_kernel, dim3((unsigned)((M->n_worlds + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     M->n_worlds, mask_dev, M->ptrs.fresh);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+static int fill_motion(nmf_motion* M, const nmf_motion_params* p, const int32_t* pairs, const float* weights, int n_pairs, int n_omm) {
+  if (n_omm < 1 || n_omm > nmf::kMaxOmmatidia) return fail("nmf_motion_create: n_omm must be in 1..1024, got " + std::to_string(n_omm));
+  if (n_pairs < 0 || n_pairs > nmf::kMotionMaxPairs) return fail("nmf_motion_create: n_pairs must be in 0..3072, got " + std::to_string(n_pairs));
+  if (n_pairs > 0 && (!pairs || !weights)) return fail("nmf_motion_create: null pairs / weights");
+  const float values[7] = {p->a_fast, p->a_slow, p->gain, p->delta, p->base, p->drive_min, p->drive_max};
+  for (float v : values)
+    if (!std::isfinite(v)) return fail("nmf_motion_create: a parameter is not finite");
+  if (p->a_fast < 0.f || p->a_fast > 1.f || p->a_slow < 0.f || p->a_slow > 1.f) return fail("nmf_motion_create: a_fast and a_slow must be in [0, 1]");
+  std::vector<int32_t> table((size_t)4 * (size_t)std::max(n_pairs, 1), 0);      // (a, b, bits of wx, bits of wy)
+  for (int k = 0; k < n_pairs; ++k) {
+    const int32_t a = pairs[2 * k], b = pairs[2 * k + 1];
+    if (a < 0 || a >= n_omm || b < 0 || b >= n_omm)
+      return fail("nmf_motion_create: pair " + std::to_string(k) + " = (" + std::to_string(a) + ", " + std::to_string(b) + ") is outside the retina's " + std::to_string(n_omm) + " ommatidia");
+    if (a == b) return fail("nmf_motion_create: pair " + std::to_string(k) + " joins ommatidium " + std::to_string(a) + " to itself (a == b)");
+    if (!std::isfinite(weights[2 * k]) || !std::isfinite(weights[2 * k + 1])) return fail("nmf_motion_create: the weight of pair " + std::to_string(k) + " is not finite");
+    table[4 * (size_t)k] = a; table[4 * (size_t)k + 1] = b;
+    std::memcpy(&table[4 * (size_t)k + 2], weights + 2 * k, 2 * sizeof(float));
+  }
+  nmf::MotionArgs& A = M->args;
+  A.p = *p;
+  A.n_worlds = M->n_worlds; A.n_omm = n_omm; A.n_pairs = n_pairs; A.den = 65536.0 * (double)n_pairs;
+  const size_t n = (size_t)M->n_worlds, cells = n * 2 * (size_t)n_omm;
+  nmf::MotionPtrs& P = M->ptrs;
+  P.pairs = (const int4*)M->mem.upload(table.data(), sizeof(int32_t) * table.size());
+  P.fast = (float*)M->mem.alloc(sizeof(float) * cells);
+  P.slow = (float*)M->mem.alloc(sizeof(float) * cells);
+  P.fresh = (uint8_t*)M->mem.alloc(n);
+  P.sums = (int*)M->mem.alloc(sizeof(int) * 4 * n);
+  P.flow = (float*)M->mem.alloc(sizeof(float) * 4 * n);
+  P.rotation = (float*)M->mem.alloc(sizeof(float) * n);
+  P.translation = (float*)M->mem.alloc(sizeof(float) * n);
+  const std::vector<float> ones(2 * n, 1.f);
+  M->drive = (float*)M->mem.upload(ones.data(), sizeof(float) * ones.size());
+  if (!M->mem.ok) return -1;
+  if (nmf_motion_reset(M, nullptr, nullptr) != 0) return -1;
+  HIP_OK(hipDeviceSynchronize());
+  return 0;
+}
+
+extern "C" nmf_motion* nmf_motion_create(nmf_batch* b, const nmf_motion_params* p, const int32_t* pairs_host, const float* weights_host,
+                                         int n_pairs, int n_omm) {
+  if (!b || !p) { fail("nmf_motion_create: null batch / params"); return nullptr; }
+  return build_or_destroy(b->mem.device, "nmf_motion_create", new nmf_motion(), nmf_motion_destroy, [&](nmf_motion* M) {
+    M->n_worlds = b->n_worlds;
+    return fill_motion(M, p, pairs_host, weights_host, n_pairs, n_omm);
+  });
+}
+
+extern "C" void* nmf_motion_field_ptr(nmf_motion* M, int which, int32_t* width) {
+  if (!M) { fail("nmf_motion_field_ptr: null handle"); return nullptr; }
+  const nmf::MotionPtrs& P = M->ptrs;
+  void* ptr[8] = {P.fast, P.slow, P.sums, P.flow, P.rotation, P.translation, M->drive, P.fresh};
+  const int32_t w[8] = {2 * M->args.n_omm, 2 * M->args.n_omm, 4, 4, 1, 1, 2, 1};
+  if (which < 0 || which > 7) { fail("nmf_motion_field_ptr: no such field"); return nullptr; }
+  if (width) *width = w[which];
+  return ptr[which];
+}
+
+// Pure stream-ordered work: one kernel launch.
+extern "C" int nmf_motion_update(nmf_motion* M, const float* omm_dev, const float* base_dev, float* drive_out_dev, void* stream) {
+  if (!M) return fail("nmf_motion_update: null handle");
+  if (!omm_dev) return fail("nmf_motion_update: null omm");
+  if (!drive_out_dev) return fail("nmf_motion_update: null drive");
+  if (((uintptr_t)omm_dev & 7) || ((uintptr_t)base_dev & 3) || ((uintptr_t)drive_out_dev & 3))
+    return fail("nmf_motion_update: omm must be 8-byte, base and drive 4-byte aligned");
+  DEVICE_GUARD(M);
+  hipLaunchKernelGGL(nmf::nmf_motion_kernel, dim3((unsigned)((M->n_worlds + nmf::kMotionWorlds - 1) / nmf::kMotionWorlds)), dim3(nmf::kMotionThreads),
+                     0, (hipStream_t)stream, M->args, M->ptrs, reinterpret_cast<const float2*>(omm_dev), base_dev, drive_out_dev);
   HIP_OK(hipGetLastError());
   return 0;
 }

@@ -22,6 +22,7 @@
 // the launch allocates nothing and replays from a captured graph.
 #include "nmf.h"
 #include "nmf_device.h"
+#include "nmf_exact.h"      // div_rn: the correctly rounded double division
 
 namespace nmf {
 
@@ -35,28 +36,12 @@ struct TaxisArgs {
   int n_worlds, n_omm, n_dims, H, W;
 };
 
-// x / y correctly rounded.  The library is compiled with -fapprox-func, under which a double division — and so __ddiv_rn, which
-// the headers define as a plain one — becomes a refined reciprocal times x with neither scaling nor fix-up, a unit in the last
-// place off now and then; no pragma takes that licence back on this target.  So the division is spelt out: the instruction
-// sequence the compiler emits for an IEEE division (checked against it instruction by instruction).
-__device__ __forceinline__ double taxis_div(double x, double y) {
-#pragma clang fp contract(off) reassociate(off)
-  bool scaled, unused;
-  const double ys = __builtin_amdgcn_div_scale(x, y, false, &unused);      // the denominator, scaled into range
-  const double xs = __builtin_amdgcn_div_scale(x, y, true, &scaled);       // the numerator
-  const double r0 = __builtin_amdgcn_rcp(ys);
-  const double r1 = __builtin_fma(r0, __builtin_fma(-ys, r0, 1.0), r0);
-  const double r2 = __builtin_fma(r1, __builtin_fma(-ys, r1, 1.0), r1);
-  const double q0 = xs * r2;
-  return __builtin_amdgcn_div_fixup(__builtin_amdgcn_div_fmas(__builtin_fma(-ys, q0, xs), r2, q0, scaled), y, x);
-}
-
 // (cy, cx, area) of one eye from its integer sums
 __device__ __forceinline__ void taxis_features(const TaxisArgs& A, int cnt, int sx, int sy, float (&f)[3]) {
   if (cnt == 0) { f[0] = 0.5f; f[1] = 0.5f; f[2] = 0.f; return; }
-  f[0] = (float)taxis_div((double)sy, (double)(16 * cnt * A.H));
-  f[1] = (float)taxis_div((double)sx, (double)(16 * cnt * A.W));
-  f[2] = (float)taxis_div((double)cnt, (double)A.n_omm);
+  f[0] = (float)div_rn((double)sy, (double)(16 * cnt * A.H));
+  f[1] = (float)div_rn((double)sx, (double)(16 * cnt * A.W));
+  f[2] = (float)div_rn((double)cnt, (double)A.n_omm);
 }
 
 // The speed factor of one side from its eye: 1 unless the eye found an object
@@ -76,7 +61,7 @@ __device__ __forceinline__ float taxis_odor_bias(const nmf_taxis_params& p, cons
     const float4 r = reinterpret_cast<const float4*>(I)[d];
     const float L = p.w_ant * r.z + p.w_palp * r.x, R = p.w_ant * r.w + p.w_palp * r.y;
     const float s = L + R;
-    const float c = s > 0.f ? (float)taxis_div((double)(L - R), (double)s) : 0.f;
+    const float c = s > 0.f ? (float)div_rn((double)(L - R), (double)s) : 0.f;
     b = b + gains[d] * c;
   }
   // A sum that starts at +0 is never -0, but the library's -fno-signed-zeros lets the compiler drop the `0 +` of the first term
@@ -117,7 +102,7 @@ nmf_taxis_kernel(TaxisArgs A, const int* __restrict__ centres, const float2* __r
   if (lane != 0) return;
   const float v[2] = {taxis_visual_speed(p, p.front_edge[0], f[0]), taxis_visual_speed(p, p.front_edge[1], f[1])};
   const float b = odor ? taxis_odor_bias(p, odor + (size_t)w * (size_t)(A.n_dims * 4), gains, A.n_dims) : 0.f;
-  const float q = (float)taxis_div((double)(b * fabsf(b)), (double)(1.f + b * b));
+  const float q = (float)div_rn((double)(b * fabsf(b)), (double)(1.f + b * b));
   const float o[2] = {1.f - p.odor_delta * fmaxf(q, 0.f), 1.f - p.odor_delta * fmaxf(-q, 0.f)};
   if (features) {
 #pragma unroll

@@ -15,9 +15,13 @@ names (``:199-200``) are not shipped, and no code exists, so the following is *b
   of a time-varying plume grid per world, advected by a noisy wind beside the physics (:class:`OdorPlume`; the reference holds
   no plume code or data: the whole model is stated in include/nmf.h and specified by tests/plume_spec.py);
 * path integration (:class:`PathIntegrator`) — heading and position from the legs' stance strides, in the form of flygym 1.x's
-  path-integration task — is stated in include/nmf.h and specified by tests/odometry_spec.py.
+  path-integration task — is stated in include/nmf.h and specified by tests/odometry_spec.py;
+* motion vision (:class:`MotionDetectors`) — two low-pass filters per ommatidium, a Hassenstein-Reichardt correlator per pair of
+  neighbouring ommatidia (:meth:`Retina.motion_pairs`), wide-field flow per eye and an optomotor drive for the ``TurningCPG`` — is
+  stated in include/nmf.h and specified by tests/motion_spec.py; the reference holds no vision processing at all.
 
-The arithmetic runs in ``libnmf_hip.so`` (``nmf_retina_resample``, ``nmf_odor_intensity``, ``nmf_plume_*``, ``nmf_odometry_*``).
+The arithmetic runs in ``libnmf_hip.so`` (``nmf_retina_resample``, ``nmf_odor_intensity``, ``nmf_plume_*``, ``nmf_odometry_*``,
+``nmf_motion_*``).
 """
 
 from __future__ import annotations
@@ -30,7 +34,7 @@ from . import _native
 from ._handle import NativeHandle, _field_view, check_params, fly_batch, leg_segments, reset_mask, site_arrays
 from .anatomy import LEGS
 
-__all__ = ["Retina", "OdorSensors", "OdorPlume", "PathIntegrator", "RAW_IMG_HEIGHT", "RAW_IMG_WIDTH", "NUM_OMMATIDIA"]
+__all__ = ["Retina", "OdorSensors", "OdorPlume", "PathIntegrator", "MotionDetectors", "RAW_IMG_HEIGHT", "RAW_IMG_WIDTH", "NUM_OMMATIDIA"]
 
 RAW_IMG_HEIGHT = 512     # flygym1_config.yaml:143
 RAW_IMG_WIDTH = 450      # :144
@@ -42,6 +46,7 @@ EYE_CAMERAS = {          # :164-173  (parent segment, offset mm, euler orientati
 }
 MAX_STEERING_SIDE = 2047          # csrc/nmf_taxis.hip: ommatidium centres are int16 sixteenths of a pixel ...
 MAX_STEERING_OMMATIDIA = 1024     # ... and at most kMaxOmmatidia of them are summed
+MAX_MOTION_PAIRS = 3072           # csrc/nmf_motion.hip: pairs of neighbouring ommatidia an eye's int32 flow sums can hold
 ODOR_SENSOR_SITES = [    # :175-192  (parent segment, offset in the segment frame, mm)
     ("c_rostrum", (-0.15, 0.15, -0.15)),     # left maxillary palp
     ("c_rostrum", (-0.15, -0.15, -0.15)),    # right maxillary palp
@@ -150,6 +155,26 @@ class Retina:
         if self.num_ommatidia > MAX_STEERING_OMMATIDIA:
             raise ValueError(f"a retina of {self.num_ommatidia} ommatidia exceeds the steering kernel's {MAX_STEERING_OMMATIDIA}")
         return np.rint(16.0 * self.ommatidia_centres()).astype(np.int16)
+
+    def motion_pairs(self, reach: float = 1.25):
+        """``(pairs (P, 2) int32, weights (P, 2) float32)``: every pair ``a < b`` of ommatidia whose centres
+        (:meth:`ommatidia_centres`) are closer than ``reach`` times the median nearest-neighbour distance, in ascending
+        ``(a, b)``, and the unit vector from ``a`` to ``b`` in image coordinates (x = column, y = row) — the neighbour list the
+        motion detectors correlate over (:class:`MotionDetectors`).  The default retina: 2070 pairs along the lattice's three
+        axes.  Refuses a retina with more than 3072 pairs or more than 1024 ommatidia."""
+        if self.num_ommatidia > MAX_STEERING_OMMATIDIA:
+            raise ValueError(f"a retina of {self.num_ommatidia} ommatidia exceeds the motion kernel's {MAX_STEERING_OMMATIDIA}")
+        c = self.ommatidia_centres()
+        if c.shape[0] < 2:
+            return np.zeros((0, 2), dtype=np.int32), np.zeros((0, 2), dtype=np.float32)
+        v = c[None, :, :] - c[:, None, :]                          # v[a, b] = centre b - centre a
+        dist = np.hypot(v[..., 0], v[..., 1])
+        pitch = np.median(np.where(np.eye(c.shape[0], dtype=bool), np.inf, dist).min(axis=1))
+        a, b = np.nonzero(np.triu(dist < float(reach) * pitch, k=1))      # (row-major: ascending a, then b)
+        if a.size > MAX_MOTION_PAIRS:
+            raise ValueError(f"{a.size} pairs within {reach} pitches exceed the motion kernel's {MAX_MOTION_PAIRS}")
+        weights = v[a, b] / dist[a, b, None]
+        return np.stack([a, b], axis=-1).astype(np.int32), weights.astype(np.float32)
 
     def hex_pxls_to_human_readable(self, readings: np.ndarray) -> np.ndarray:
         """Paint ``(num_ommatidia, 2)`` readings back onto the pixel grid (for inspection)."""
@@ -469,3 +494,125 @@ class PathIntegrator(NativeHandle):
         a, r2_h = fit(A_h, dh.reshape(-1))
         b, r2_d = fit(A_d, dd.reshape(-1))
         return np.concatenate([a[:3], -a[:3], b[:3], b[:3], [a[3], b[3]]]), r2_h, r2_d
+
+
+class _MotionParams(ctypes.Structure):
+    """``nmf_motion_params`` of include/nmf.h."""
+
+    _fields_ = [("a_fast", ctypes.c_float), ("a_slow", ctypes.c_float), ("gain", ctypes.c_float), ("delta", ctypes.c_float),
+                ("base", ctypes.c_float), ("drive_min", ctypes.c_float), ("drive_max", ctypes.c_float), ("front_edge", ctypes.c_int32 * 2)]
+
+
+class MotionDetectors(NativeHandle):
+    """Motion vision on the GPU (``nmf_motion_*``, ``csrc/nmf_motion.hip``): how the image of each eye moves, and an optomotor
+    drive that turns the fly with the panorama so that it holds its course.
+
+    Build-defined (the reference ships no vision processing) and pinned by nothing; the statement of the model is include/nmf.h
+    (``nmf_motion_update``), its specification in numpy tests/motion_spec.py.  One :meth:`update` per control tick, from the
+    ommatidia readings of both eyes (``EyeRenderer.render_into``)::
+
+        x_i = the reading of ommatidium i;  a world's first update starts from fast_i = slow_i = x_i
+        fast_i += a_fast (x_i - fast_i);  slow_i += a_slow (x_i - slow_i);  hp_i = x_i - slow_i     (a = 1 - exp(-dt / tau))
+        d_k = fast_a hp_b - hp_a fast_b                           per pair k = (a, b) of neighbouring ommatidia
+        H = mean_k d_k wx_k,  V = mean_k d_k wy_k                 per eye ((wx, wy): the unit vector from a to b in the image);
+                                                                  each term clamped to +-4 and rounded to 2^-16, summed as integers
+        ftb = -H where the image's last column faces forward (``front_edge``), else H       (the flow from front to back)
+        rotation = ftb_left - ftb_right   (positive: the panorama turns counter-clockwise about the fly);  translation = their sum
+        r = gain rotation;  q = r / (1 + |r|);  o_left = 1 - delta max(q, 0);  o_right = 1 - delta max(-q, 0)
+        drive[side] = clip(base[side] o_side, drive_min, drive_max)                         (side 0 = left, as ``TurningCPG.drive``)
+
+    so the side the panorama drifts towards is slowed and the fly turns with it.
+
+    Args:
+        sim: the batch; a world with several flies resolves to ``sim.for_fly(fly_name)``.
+        fly_name: the fly whose eyes are read.
+        dt: the control tick, seconds between two updates.
+        retina: the retina whose readings :meth:`update` takes (default: the default :class:`Retina`); at most 1024 ommatidia.
+        pairs: ``(pairs (P, 2) int, weights (P, 2) float)`` instead of ``retina.motion_pairs()``; at most 3072 pairs.
+        tau_fast, tau_slow: time constants of the two low-pass filters, seconds.
+        gain: the rotation at which a side is slowed by ``delta / 2`` is ``1 / gain``.  The default of 320 puts that point at the
+            rotation signal the curving open-loop gait itself produces over a checker ground (about 3e-3): chosen from the sweep
+            of closed-loop walks recorded in profiles/motion_summary.md.
+        delta: the largest share a side is slowed by; 0 switches the reflex off (the drive is ``base``).
+        base: the drive without rotation (or pass a tensor to :meth:`update`).
+
+    ``flow`` ``(n, 2, 2)`` (H, V per eye), ``rotation`` and ``translation`` ``(n,)``, ``drive`` ``(n, 2)`` float32, ``sums``
+    ``(n, 2, 2)`` int32 (the integer flow sums), the filter states ``fast`` and ``slow`` ``(n, 2, n_omm)`` float32 and ``fresh``
+    ``(n,)`` uint8 are zero-copy views of the handle's device memory, allocated once.  Every method is stream-ordered device work on
+    the simulation's stream; :meth:`update` is one launch and can be captured in a graph.  Close it before its simulation.
+    """
+
+    _destroy_entry, _noun = "nmf_motion_destroy", "motion detector"
+    _views = ("fast", "slow", "sums", "flow", "rotation", "translation", "drive", "fresh")
+
+    def __init__(self, sim, fly_name: str, *, dt: float, retina=None, pairs=None, tau_fast: float = 0.035, tau_slow: float = 0.15,
+                 gain: float = 320.0, delta: float = 0.8, base: float = 1.0, drive_min: float = 0.2, drive_max: float = 1.2):
+        from .controllers import eye_front_edges
+
+        sim = fly_batch(sim, fly_name, resolve=True)
+        if fly_name not in sim.world.fly_lookup:
+            raise ValueError(f"no fly named {fly_name!r} in this simulation ({', '.join(sim.world.fly_lookup)})")
+        if not (dt > 0 and tau_fast > 0 and tau_slow > 0):
+            raise ValueError(f"dt, tau_fast and tau_slow must be positive, got {dt!r}, {tau_fast!r}, {tau_slow!r}")
+        self.sim, self.fly_name = sim, fly_name
+        self.retina = retina or Retina()
+        self.n_worlds, self.n_omm = int(sim.n_worlds), int(self.retina.num_ommatidia)
+        if self.n_omm > MAX_STEERING_OMMATIDIA:
+            raise ValueError(f"a retina of {self.n_omm} ommatidia exceeds the motion kernel's {MAX_STEERING_OMMATIDIA}")
+        pr, wt = self.retina.motion_pairs() if pairs is None else pairs
+        pr, wt = np.asarray(pr), np.asarray(wt)
+        if pr.ndim != 2 or pr.shape[1] != 2 or wt.shape != pr.shape or not np.issubdtype(pr.dtype, np.integer):
+            raise ValueError(f"pairs takes (pairs (P, 2) int, weights (P, 2) float), got {pr.shape} {pr.dtype} and {wt.shape} {wt.dtype}")
+        if pr.shape[0] > MAX_MOTION_PAIRS:
+            raise ValueError(f"{pr.shape[0]} pairs exceed the motion kernel's {MAX_MOTION_PAIRS}")
+        if pr.size and (pr.min() < 0 or pr.max() >= self.n_omm):
+            raise ValueError(f"a pair index lies outside the retina's {self.n_omm} ommatidia")
+        if (pr[:, 0] == pr[:, 1]).any():
+            raise ValueError("a pair joins an ommatidium to itself (a == b)")
+        self.pairs = np.ascontiguousarray(pr, dtype=np.int32)
+        self.weights = np.ascontiguousarray(wt, dtype=np.float32)
+        self.n_pairs = int(self.pairs.shape[0])
+        self.dt, self.front_edge = float(dt), eye_front_edges()
+        self.a_fast = np.float32(1.0 - np.exp(-np.float64(dt) / np.float64(tau_fast)))
+        self.a_slow = np.float32(1.0 - np.exp(-np.float64(dt) / np.float64(tau_slow)))
+        check_params(_MotionParams, "nmf_motion_params_size", "sensors.py")
+        self._params = _MotionParams(float(self.a_fast), float(self.a_slow), float(gain), float(delta), float(base), float(drive_min),
+                                     float(drive_max), (ctypes.c_int32 * 2)(*self.front_edge))
+        h = self._create("nmf_motion_create", sim._batch_h, ctypes.byref(self._params), self.pairs.ctypes.data if self.n_pairs else None,
+                         self.weights.ctypes.data if self.n_pairs else None, self.n_pairs, self.n_omm)
+        n = self.n_worlds
+        view = lambda which, shape, typestr="<f4": _field_view(sim, _native.lib().nmf_motion_field_ptr, h, which, typestr, shape)
+        self.fast, self.slow = view(0, (n, 2, self.n_omm)), view(1, (n, 2, self.n_omm))
+        self.sums, self.flow = view(2, (n, 2, 2), "<i4"), view(3, (n, 2, 2))
+        self.rotation, self.translation = view(4, (n,)), view(5, (n,))
+        self.drive, self.fresh = view(6, (n, 2)), view(7, (n,), "|u1")
+
+    def _checked(self, name, x, shape):
+        t = self.sim._torch
+        if (not isinstance(x, t.Tensor) or tuple(x.shape) != shape or x.dtype != t.float32 or x.device != self.sim.device
+                or not x.is_contiguous()):
+            got = f"{tuple(x.shape)} {x.dtype} on {x.device}" if isinstance(x, t.Tensor) else type(x).__name__
+            raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape} on {self.sim.device}, got {got}")
+        return x
+
+    def update(self, omm, base=None, out=None):
+        """One update from ``omm`` ``(n_worlds, 2, num_ommatidia, 2)`` (float32, contiguous, on the simulation's device): one kernel
+        launch on the simulation's stream, no allocation — capturable.  Advances :attr:`fast` and :attr:`slow`, writes
+        :attr:`sums`, :attr:`flow`, :attr:`rotation` and :attr:`translation`, and the drive into ``out`` ``(n_worlds, 2)`` (for
+        example ``cpg.drive``) or into :attr:`drive`; returns the drive tensor.  ``base`` ``(n_worlds, 2)`` (for example
+        ``SensorySteering.drive``) takes the place of the scalar parameter ``base``."""
+        h, n = self._handle(), self.n_worlds
+        self._checked("omm", omm, (n, 2, self.n_omm, 2))
+        if base is not None:
+            self._checked("base", base, (n, 2))
+        drive = self.drive if out is None else self._checked("out", out, (n, 2))
+        _native.check(_native.lib().nmf_motion_update(h, omm.data_ptr(), None if base is None else base.data_ptr(), drive.data_ptr(),
+                                                      self.sim._stream()))
+        return drive
+
+    def reset(self, mask=None) -> None:
+        """The worlds of ``mask`` (``(n_worlds,)`` bool, numpy or torch; default all) forget their filters: their next update starts
+        from its readings, as a first update does.  The others keep their state."""
+        h = self._handle()
+        m = reset_mask(mask, self.n_worlds, self.sim)
+        _native.check(_native.lib().nmf_motion_reset(h, None if m is None else m.data_ptr(), self.sim._stream()))

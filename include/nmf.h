@@ -29,6 +29,7 @@ typedef struct nmf_camera_plan nmf_camera_plan;
 typedef struct nmf_cpg nmf_cpg;
 typedef struct nmf_plume nmf_plume;
 typedef struct nmf_odometry nmf_odometry;
+typedef struct nmf_motion nmf_motion;
 
 /* Per-world fields addressable through nmf_field_ptr / nmf_gather_* */
 enum nmf_field {
@@ -667,6 +668,75 @@ int nmf_odometry_update(nmf_odometry* odometry, void* stream);
 #define NMF_ODOMETRY_COUNT 5      /* [1] int32                                                                */
 #define NMF_ODOMETRY_COEF 6       /* ONE row of 14 float64 shared by all worlds (width 14; not per world)     */
 void* nmf_odometry_field_ptr(nmf_odometry* odometry, int which, int32_t* width);
+
+/* Motion vision with its state on the device (flygym_amd.sensors.MotionDetectors; csrc/nmf_motion.hip): how the image of each eye
+ * moves, from correlating neighbouring ommatidia over time, and an optomotor drive that turns the fly with the panorama so that it
+ * holds its course.  No reference counterpart (the snapshot holds no vision processing): build-defined and pinned by nothing
+ * (specification tests/motion_spec.py).
+ * Shared by all worlds of a handle: a list of n_pairs pairs (a_k, b_k, wx_k, wy_k) — two neighbouring ommatidia a != b and the
+ * float32 unit vector from a to b in image coordinates (x = column, y = row).  State per world: a "fresh" byte and, per eye and
+ * ommatidium, two float32 low-pass states fast and slow.  One update (one launch per control tick), per world:
+ *   per eye e (0 left, 1 right), over the ommatidia i of omm[w][e][i][2]:
+ *     x_i = omm[i][0] + omm[i][1]                            (one channel is always 0, so the sum is the reading)
+ *     if the world is fresh: fast_i = slow_i = x_i
+ *     fast_i <- fast_i + fl(a_fast fl(x_i - fast_i)),  slow_i <- slow_i + fl(a_slow fl(x_i - slow_i)),  hp_i = x_i - slow_i(new)
+ *   per eye, over the pairs k, with the values just computed (a Hassenstein-Reichardt correlator per pair):
+ *     d_k = fl(fast_a hp_b) - fl(hp_a fast_b)
+ *     Sx += (int32) rint(min(max(fl(d_k wx_k), -4), 4) 65536),  Sy likewise with wy_k
+ *       (terms of resolution 2^-16 clamped to +-4, a NaN counting as -4: with n_pairs <= 3072 a sum stays below 2^30 for any
+ *        readings, and integer sums do not depend on the order of the reduction)
+ *     H_e = Sx / (65536 n_pairs), V_e = Sy / (65536 n_pairs)  (each: the correctly rounded float64 division of the exact
+ *                                                              operands, rounded once to float32); 0 when n_pairs = 0
+ *   ftb_e = front_edge[e] ? -H_e : H_e                       (the flow from front to back across eye e)
+ *   rotation = ftb_0 - ftb_1     (positive when the panorama turns counter-clockwise about the fly, seen from above)
+ *   translation = ftb_0 + ftb_1                              (a zero of either is +0)
+ *   r = gain rotation;  q = r / (1 + |r|) (correctly rounded as above);  o_0 = 1 - delta max(q, 0), o_1 = 1 - delta max(-q, 0)
+ *   drive[side] = min(max(base[side] o_side, drive_min), drive_max)      (side 0 = left: the order of NMF_CPG_DRIVE; base[side]
+ *                                                                         from base_dev, or the parameter `base` without it)
+ *   the world is no longer fresh
+ * So a counter-clockwise panorama slows the left side and the fly turns with it.  Every float32 operation is rounded as written
+ * (no contraction, no reassociation): state and outputs equal the specification's bit for bit.  a_fast and a_slow are
+ * 1 - exp(-dt / tau) of the caller's control tick dt, computed in float64 on the host and rounded once to float32. */
+typedef struct nmf_motion_params {
+  float a_fast, a_slow;         /* low-pass coefficients of the two filters (defaults: tau 35 ms and 150 ms)              */
+  float gain, delta;            /* optomotor rule: r = gain rotation; a side is slowed by at most delta                    */
+  float base, drive_min, drive_max;
+  int32_t front_edge[2];        /* per eye: 1 when the image's LAST column faces forward, 0 when column 0 does             */
+} nmf_motion_params;
+
+/* sizeof(nmf_motion_params) as this library was compiled (as nmf_eye_params_size). */
+size_t nmf_motion_params_size(void);
+
+/* An explicit handle for the worlds of `batch`, on its device.  pairs_host[n_pairs][2] int32 and weights_host[n_pairs][2] float32
+ * are HOST memory (either may be NULL when n_pairs is 0), copied.  Owns the pair list, the state and the outputs; every world
+ * starts fresh.  NOT stream-ordered (allocations, synchronous uploads); must not be called inside a stream capture.  NULL on error
+ * (nmf_last_error), with nothing left allocated: n_omm outside 1..1024; n_pairs outside 0..3072; a pair index outside 0..n_omm-1;
+ * a pair with a == b; a weight or a parameter that is not finite; a_fast or a_slow outside [0, 1]; no device memory. */
+nmf_motion* nmf_motion_create(nmf_batch* batch, const nmf_motion_params* params, const int32_t* pairs_host,
+                              const float* weights_host, int n_pairs, int n_omm);
+void nmf_motion_destroy(nmf_motion* motion);
+
+/* The worlds with mask_dev[w] != 0 (uint8 per world, device memory; NULL: all) become fresh: their next update starts both
+ * filters from its readings, exactly as a first update does.  The others are not touched.  Stream-ordered. */
+int nmf_motion_reset(nmf_motion* motion, const uint8_t* mask_dev, void* stream);
+
+/* One update of every world from omm_dev[n_worlds][2][n_omm][2] float32 (8-byte aligned): argument checks and ONE kernel launch on
+ * `stream`, no allocation, no host synchronisation, hipGraph-capturable (the fresh bytes live on the device, so a captured update
+ * replays correctly).  base_dev[n_worlds][2] float32 or NULL (the parameter `base`); the drive goes to drive_out_dev[n_worlds][2]
+ * float32 (for example NMF_CPG_DRIVE, or the handle's own NMF_MOTION_DRIVE).  Refused: a null handle, omm or drive; a misaligned
+ * buffer. */
+int nmf_motion_update(nmf_motion* motion, const float* omm_dev, const float* base_dev, float* drive_out_dev, void* stream);
+
+/* Device pointer + row width of an array of the handle (zero-copy views; writable between launches). */
+#define NMF_MOTION_FAST 0         /* [2][n_omm] float32                                                        */
+#define NMF_MOTION_SLOW 1         /* [2][n_omm] float32                                                        */
+#define NMF_MOTION_SUMS 2         /* [2][2] int32: Sx, Sy per eye                                              */
+#define NMF_MOTION_FLOW 3         /* [2][2] float32: H, V per eye                                              */
+#define NMF_MOTION_ROTATION 4     /* [1] float32                                                               */
+#define NMF_MOTION_TRANSLATION 5  /* [1] float32                                                               */
+#define NMF_MOTION_DRIVE 6        /* [2] float32: a drive buffer of the handle's own (starts at 1)             */
+#define NMF_MOTION_FRESH 7        /* [1] uint8                                                                 */
+void* nmf_motion_field_ptr(nmf_motion* motion, int which, int32_t* width);
 
 /* Odor intensity at n_sensors points rigidly attached to named segments (sensor_seg = index into the
  * batch's segment order, sensor_rel = offset in the segment frame): out[w][d][k] = sum_s peak[s][d] / dist^2.
