@@ -35,6 +35,10 @@ sensors once per launch; the oscillators are not changed by them.
 ``SensorySteering`` closes the loop from the senses: one stateless launch (``csrc/nmf_taxis.hip``; specification
 ``tests/taxis_spec.py``) turns the ommatidia readings of both eyes and the readings of the four odor sites into the drive of a
 ``TurningCPG`` — flygym 1.x's visual taxis and odor taxis, build-defined and pinned by nothing.
+
+``PlumeNavigator`` steers the CPG through an intermittent plume: a stochastic walk / stop / turn state machine per world, driven by
+odor onsets and biased upwind, with its state and its noise counter on the device (``csrc/nmf_navigator.hip``; specification
+``tests/navigator_spec.py``) — the navigator of flygym 1.x's plume-tracking task, build-defined and pinned by nothing.
 """
 
 from __future__ import annotations
@@ -48,7 +52,7 @@ from ._handle import NativeHandle, _field_view, check_params, fly_batch, leg_seg
 from .anatomy import LEGS, JointDOF
 from .replay import MotionSnippet
 
-__all__ = ["TripodCPG", "TurningCPG", "HybridTurningCPG", "SensorySteering"]
+__all__ = ["TripodCPG", "TurningCPG", "HybridTurningCPG", "SensorySteering", "PlumeNavigator", "navigator_constants"]
 
 TRIPOD_PHASE_BIAS = {"lf": 0.0, "rm": 0.0, "lh": 0.0, "rf": np.pi, "lm": np.pi, "rh": np.pi}
 
@@ -513,3 +517,148 @@ class SensorySteering:
             None if omm is None else omm.data_ptr(), odor_ptr, self._gains.data_ptr(), self.n_dims, n,
             self.features.data_ptr(), self.bias.data_ptr(), drive.data_ptr(), self.sim._stream()))
         return drive
+
+
+class _NavigatorParams(ctypes.Structure):
+    """``nmf_navigator_params`` of include/nmf.h."""
+
+    _fields_ = [("seed", ctypes.c_uint32), ("first_world", ctypes.c_int32), ("root_seg", ctypes.c_int32), ("odor_dim", ctypes.c_int32),
+                ("turn_ticks", ctypes.c_int32), ("dt", ctypes.c_float), ("threshold", ctypes.c_float), ("decay_stop", ctypes.c_float),
+                ("decay_walk", ctypes.c_float), ("decay_freq", ctypes.c_float), ("inv_tau_freq", ctypes.c_float),
+                ("lambda_ws0", ctypes.c_float), ("dlambda_ws", ctypes.c_float), ("lambda_sw0", ctypes.c_float),
+                ("dlambda_sw", ctypes.c_float), ("lambda_turn", ctypes.c_float), ("p_up0", ctypes.c_float), ("up_gain", ctypes.c_float),
+                ("p_up_min", ctypes.c_float), ("p_up_max", ctypes.c_float), ("walk_drive", ctypes.c_float * 2),
+                ("stop_drive", ctypes.c_float * 2), ("turn_drive", ctypes.c_float * 2)]
+
+
+def navigator_constants(tick_s: float, tau_stop: float, tau_walk: float, tau_freq: float, turn_duration: float) -> dict:
+    """What :class:`PlumeNavigator` derives from its time constants, computed in float64 and rounded once to float32 — the kernel
+    neither divides nor calls ``exp``: ``decay_x = exp(-tick_s / tau_x)``, ``inv_tau_freq = 1 / tau_freq`` and
+    ``turn_ticks = round(turn_duration / tick_s)``."""
+    dt = float(tick_s)
+    taus = dict(stop=float(tau_stop), walk=float(tau_walk), freq=float(tau_freq))
+    if not (np.isfinite(dt) and dt > 0):
+        raise ValueError(f"tick_s must be positive and finite, got {tick_s!r}")
+    for name, tau in taus.items():
+        if not (np.isfinite(tau) and tau > 0):
+            raise ValueError(f"tau_{name} must be positive and finite, got {tau!r}")
+    if not np.isfinite(float(turn_duration)):
+        raise ValueError(f"turn_duration must be finite, got {turn_duration!r}")
+    out = {f"decay_{name}": np.float32(np.exp(-dt / tau)) for name, tau in taus.items()}
+    out["inv_tau_freq"] = np.float32(1.0 / taus["freq"])
+    out["turn_ticks"] = int(round(float(turn_duration) / dt))
+    if not 1 <= out["turn_ticks"] <= 65535:
+        raise ValueError(f"turn_duration / tick_s must round to 1..65535 ticks, got {out['turn_ticks']}")
+    return out
+
+
+class PlumeNavigator(NativeHandle):
+    """Navigating an intermittent odor plume on the GPU (``nmf_navigator_*``): per world a stochastic walk / stop / turn state
+    machine driven by odor onsets ("encounters"), in the form of Demir et al. 2020 as flygym 1.x steered its plume-tracking task
+    with it, that writes the drive of a :class:`TurningCPG`.
+
+    Build-defined and pinned by nothing (the reference ships no controllers; nothing is claimed about matching flygym 1.x); the
+    statement of the model is include/nmf.h (``nmf_navigator_update``), its specification in numpy tests/navigator_spec.py.  One
+    :meth:`update` per control tick, from the antennal readings, the wind and the root segment's attitude::
+
+        e = the antennal sum I[2] + I[3] rose above ``threshold`` in this update                   (an encounter)
+        k_stop <- k_stop decay_stop + e;  k_walk <- k_walk decay_walk + e;  freq <- freq decay_freq + e / tau_freq
+        p_stop = clip(dt (stop_rate[0] + stop_rate[1] k_stop), 0, 1);  p_walk likewise from walk_rate and k_walk
+        p_turn = clip(dt turn_rate, 0, 1);  p_up = clip(p_up[0] + p_up[1] freq, p_up_bounds)
+        walking: stop with p_stop, else turn with p_turn for ``turn_duration`` — upwind with p_up, else downwind; stopped: walk with p_walk
+        drive = walk_drive, stop_drive or turn_drive = (inner, outer) by the new state
+
+    The three uniform draws of a tick are a counter-based hash of ``(seed, first_world + w, ticks[w])`` — the plume's, with its
+    own draw indices —, so a world's decisions do not depend on the batch it is stepped in and a captured update draws fresh
+    noise on every replay.
+
+    Args:
+        sim: the batch; for a world with several flies ``sim.for_fly(fly_name)``.
+        fly_name: the fly that is steered (its root segment's attitude is read).
+        tick_s: the control tick in seconds (one :meth:`update` per tick).
+        threshold: of the antennal sum, in the readings' unit.
+        seed, first_world: the noise streams; ``first_world`` places a shard of worlds inside a larger population.
+        odor_dim: the odor dimension whose antennae are read (0..7).
+        stop_rate, walk_rate: ``(base, change per unit of the filter)`` per second; turn_rate per second.
+        tau_stop, tau_walk, tau_freq: the filters' time constants in seconds; turn_duration in seconds.
+        p_up: ``(base, gain per unit of freq)``; p_up_bounds: ``(min, max)`` in [0, 1].
+        walk_drive, stop_drive: ``(left, right)``; turn_drive: ``(inner, outer)``.
+
+    The default rates and time constants are Demir et al.'s as flygym 1.x's tutorial used them, as remembered (its source is not at
+    hand); the upwind probability is this project's linear stand-in for their sigmoid.  ``state`` (0 walk, 1 stop, 2 turn left,
+    3 turn right), ``remaining``, ``encounters`` ``(n,)`` int32, ``above`` ``(n,)`` uint8, ``k_stop``, ``k_walk``, ``freq`` ``(n,)``
+    float32, ``ticks`` ``(n,)`` (the device's uint32 counter seen as int32, as ``OdorPlume.ticks``) and ``drive`` ``(n, 2)`` float32 are zero-copy views of the device state, writable between
+    launches.  Every method is stream-ordered device work on the simulation's stream; :meth:`update` is one launch and can be
+    captured in a graph.  Close the navigator before its simulation.
+    """
+
+    WALK, STOP, TURN_LEFT, TURN_RIGHT = 0, 1, 2, 3
+    _destroy_entry, _noun = "nmf_navigator_destroy", "navigator"
+    _views = ("state", "remaining", "above", "k_stop", "k_walk", "freq", "ticks", "encounters", "drive")
+
+    def __init__(self, sim, fly_name: str, *, tick_s: float, threshold: float, seed: int = 0, first_world: int = 0, odor_dim: int = 0,
+                 stop_rate=(0.78, -0.61), walk_rate=(0.29, 0.41), turn_rate: float = 1.33, tau_stop: float = 0.2, tau_walk: float = 0.52,
+                 tau_freq: float = 2.0, turn_duration: float = 0.25, p_up=(0.5, 0.15), p_up_bounds=(0.05, 0.95),
+                 walk_drive=(1.0, 1.0), stop_drive=(0.0, 0.0), turn_drive=(-0.4, 1.2)):
+        sim = fly_batch(sim, fly_name, resolve=False)
+        if fly_name not in sim.world.fly_lookup:
+            raise ValueError(f"no fly named {fly_name!r} in this simulation ({', '.join(sim.world.fly_lookup)})")
+        for name, pair in (("stop_rate", stop_rate), ("walk_rate", walk_rate), ("p_up", p_up), ("p_up_bounds", p_up_bounds),
+                           ("walk_drive", walk_drive), ("stop_drive", stop_drive), ("turn_drive", turn_drive)):
+            if len(pair) != 2:
+                raise ValueError(f"{name} takes two values, got {pair!r}")
+        self.sim, self.fly_name = sim, fly_name
+        self.n_worlds, self.tick_s = int(sim.n_worlds), float(tick_s)
+        self.seed, self.first_world, self.odor_dim = int(seed) & 0xFFFFFFFF, int(first_world), int(odor_dim)
+        self.constants = navigator_constants(tick_s, tau_stop, tau_walk, tau_freq, turn_duration)
+        self.root_seg, _ = leg_segments(sim.world.fly_lookup[fly_name], LEGS)
+        check_params(_NavigatorParams, "nmf_navigator_params_size", "controllers.py")
+        pair = lambda v: (ctypes.c_float * 2)(float(v[0]), float(v[1]))
+        c = self.constants
+        self._params = _NavigatorParams(
+            self.seed, self.first_world, self.root_seg, self.odor_dim, c["turn_ticks"], self.tick_s, float(threshold),
+            float(c["decay_stop"]), float(c["decay_walk"]), float(c["decay_freq"]), float(c["inv_tau_freq"]), float(stop_rate[0]),
+            float(stop_rate[1]), float(walk_rate[0]), float(walk_rate[1]), float(turn_rate), float(p_up[0]), float(p_up[1]),
+            float(p_up_bounds[0]), float(p_up_bounds[1]), pair(walk_drive), pair(stop_drive), pair(turn_drive))
+        h = self._create("nmf_navigator_create", sim._batch_h, ctypes.byref(self._params))
+        view = lambda which, typestr: _field_view(sim, _native.lib().nmf_navigator_field_ptr, h, which, typestr)
+        flat = lambda which, typestr: view(which, typestr).reshape(self.n_worlds)
+        self.state, self.remaining, self.above = flat(0, "<i4"), flat(1, "<i4"), flat(2, "|u1")
+        self.k_stop, self.k_walk, self.freq = flat(3, "<f4"), flat(4, "<f4"), flat(5, "<f4")
+        self.ticks, self.encounters, self.drive = flat(6, "<i4"), flat(7, "<i4"), view(8, "<f4")
+
+    def _checked(self, name, x, shapes):
+        t = self.sim._torch
+        if (not isinstance(x, t.Tensor) or tuple(x.shape) not in shapes or x.dtype != t.float32 or x.device != t.device(self.sim.device)
+                or not x.is_contiguous()):
+            got = f"{tuple(x.shape)} {x.dtype} on {x.device}" if isinstance(x, t.Tensor) else type(x).__name__
+            raise ValueError(f"{name} must be a contiguous float32 tensor of shape {' or '.join(map(str, shapes))} on {self.sim.device}, "
+                             f"got {got}")
+        return x
+
+    def update(self, odor, wind, out=None):
+        """One update of every world from ``odor`` ``(n_worlds, n_dims, 4)`` (``OdorPlume.get_odor_intensities`` /
+        ``OdorSensors``) and ``wind`` ``(n_worlds, 2)``, ``(1, 2)`` or ``(2,)`` (``OdorPlume.wind``; one row is shared by all
+        worlds), float32, contiguous, on the simulation's device; the root segment's attitude is the batch's as it stands.  One
+        kernel launch, no allocation — capturable.  Writes the drive into ``out`` ``(n_worlds, 2)`` (for example ``cpg.drive``)
+        or into :attr:`drive`; returns the drive tensor."""
+        h = self._handle()
+        n = self.n_worlds
+        t = self.sim._torch
+        if isinstance(odor, t.Tensor) and odor.ndim == 3 and tuple(odor.shape[::2]) == (n, 4) and int(odor.shape[1]) <= self.odor_dim:
+            raise ValueError(f"odor has {int(odor.shape[1])} dimensions, the navigator reads dimension {self.odor_dim}")
+        n_dims = int(odor.shape[1]) if isinstance(odor, t.Tensor) and odor.ndim == 3 else self.odor_dim + 1
+        self._checked("odor", odor, ((n, n_dims, 4),))
+        self._checked("wind", wind, ((n, 2), (1, 2), (2,)))
+        drive = self.drive if out is None else self._checked("out", out, ((n, 2),))
+        rows = n if tuple(wind.shape) == (n, 2) else 1
+        _native.check(_native.lib().nmf_navigator_update(h, odor.data_ptr(), n_dims, wind.data_ptr(), rows,
+                                                         None if out is None else out.data_ptr(), self.sim._stream()))
+        return drive
+
+    def reset(self, mask=None) -> None:
+        """The worlds of ``mask`` (``(n_worlds,)`` bool, numpy or torch; default all) start again: walking, empty filters, tick 0
+        (their noise stream from its start), no encounters, the walk drive in :attr:`drive`; the others keep their state."""
+        h = self._handle()
+        m = reset_mask(mask, self.n_worlds, self.sim)
+        _native.check(_native.lib().nmf_navigator_reset(h, None if m is None else m.data_ptr(), self.sim._stream()))

@@ -20,9 +20,9 @@
 #include "nmf_step.hip"
 #include "nmf_sensors.hip"
 // `#pragma clang fp reassociate(off)` at file scope holds from the first file that sets it to the end of the translation unit:
-// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip, nmf_plume.hip, nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip and the host code
+// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip, nmf_plume.hip, nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip, nmf_navigator.hip and the host code
 // below are all compiled under it, and the files above are not.  Which files it covers decides their kernels' arithmetic: keep the
-// order (nmf_taxis.hip, nmf_odometry.hip and nmf_motion.hip add pragmas inside their functions only: nothing of them reaches past the file).
+// order (nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip and nmf_navigator.hip add pragmas inside their functions only: nothing of them reaches past the file).
 #include "nmf_eyes.hip"
 #include "nmf_camera.hip"
 #include "nmf_replay.hip"
@@ -31,6 +31,7 @@
 #include "nmf_taxis.hip"
 #include "nmf_odometry.hip"
 #include "nmf_motion.hip"
+#include "nmf_navigator.hip"
 #include "nmf_skeleton.h"      // nmf_model, the blob parser, classify_skeleton
 #endif
 
@@ -63,7 +64,7 @@ struct DeviceGuard {
   DeviceGuard guard_((b)->mem.device);                                                        \
   if (guard_.err != hipSuccess) return fail(std::string("hipSetDevice: ") + hipGetErrorString(guard_.err))
 
-// The device memory of one handle (batch, eye plan, camera plan, CPG, plume, odometry, motion): every allocation is 16-byte granular, recorded, and freed
+// The device memory of one handle (batch, eye plan, camera plan, CPG, plume, odometry, motion, navigator): every allocation is 16-byte granular, recorded, and freed
 // with the handle.  The first failure sets the error text, named after the entry point `who`, and sticks: later calls return
 // null without touching the device, so that a caller tests `ok` once after its last allocation.
 struct DevMem {
@@ -1738,6 +1739,106 @@ extern "C" int nmf_motion_update(nmf_motion* M, const float* omm_dev, const floa
   DEVICE_GUARD(M);
   hipLaunchKernelGGL(nmf::nmf_motion_kernel, dim3((unsigned)((M->n_worlds + nmf::kMotionWorlds - 1) / nmf::kMotionWorlds)), dim3(nmf::kMotionThreads),
                      0, (hipStream_t)stream, M->args, M->ptrs, reinterpret_cast<const float2*>(omm_dev), base_dev, drive_out_dev);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// ---- plume navigation (nmf_navigator.hip) ----
+// The per-world state; the batch lends its seg_xquat array to every update.
+struct nmf_navigator {
+  int n_worlds = 0;
+  nmf::NavArgs args{};
+  nmf::NavPtrs ptrs{};
+  DevMem mem;
+};
+
+extern "C" size_t nmf_navigator_params_size(void) { return sizeof(nmf_navigator_params); }
+
+extern "C" void nmf_navigator_destroy(nmf_navigator* N) {
+  if (!N) return;
+  N->mem.release();
+  delete N;
+}
+
+extern "C" int nmf_navigator_reset(nmf_navigator* N, const uint8_t* mask_dev, void* stream) {
+  if (!N) return fail("nmf_navigator_reset: null navigator");
+  DEVICE_GUARD(N);
+  hipLaunchKernelGGL(nmf::nmf_navigator_reset_kernel, dim3((unsigned)((N->n_worlds + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     N->args, N->ptrs, mask_dev);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+static int fill_navigator(nmf_navigator* N, const nmf_batch* b, const nmf_navigator_params* p) {
+  const float values[21] = {p->dt, p->threshold, p->decay_stop, p->decay_walk, p->decay_freq, p->inv_tau_freq, p->lambda_ws0, p->dlambda_ws,
+                            p->lambda_sw0, p->dlambda_sw, p->lambda_turn, p->p_up0, p->up_gain, p->p_up_min, p->p_up_max,
+                            p->walk_drive[0], p->walk_drive[1], p->stop_drive[0], p->stop_drive[1], p->turn_drive[0], p->turn_drive[1]};
+  for (float v : values)
+    if (!std::isfinite(v)) return fail("nmf_navigator_create: a parameter is not finite");
+  if (p->threshold < 0.f) return fail("nmf_navigator_create: threshold must not be negative");
+  const float decays[3] = {p->decay_stop, p->decay_walk, p->decay_freq};
+  for (float d : decays)
+    if (d < 0.f || d > 1.f) return fail("nmf_navigator_create: decay_stop, decay_walk and decay_freq must be in [0, 1]");
+  if (p->p_up_min < 0.f || p->p_up_max > 1.f || p->p_up_min > p->p_up_max)
+    return fail("nmf_navigator_create: p_up_min and p_up_max must be in [0, 1] with p_up_min <= p_up_max");
+  if (p->turn_ticks < 1 || p->turn_ticks > 65535) return fail("nmf_navigator_create: turn_ticks must be in 1..65535, got " + std::to_string(p->turn_ticks));
+  const int nseg = b->model->nseg;
+  if (p->root_seg < 0 || p->root_seg >= nseg) return fail("nmf_navigator_create: root_seg " + std::to_string(p->root_seg) + " is outside the batch's " + std::to_string(nseg) + " segments");
+  if (p->odor_dim < 0 || p->odor_dim > 7) return fail("nmf_navigator_create: odor_dim must be in 0..7, got " + std::to_string(p->odor_dim));
+  if (p->first_world < 0) return fail("nmf_navigator_create: first_world must not be negative");
+  nmf::NavArgs& A = N->args;
+  A.p = *p;
+  A.n_worlds = N->n_worlds; A.nseg = nseg;
+  const size_t n = (size_t)N->n_worlds;
+  nmf::NavPtrs& P = N->ptrs;
+  P.seg_xquat = b->st.seg_xquat;
+  P.state = (int*)N->mem.alloc(sizeof(int) * n);
+  P.remaining = (int*)N->mem.alloc(sizeof(int) * n);
+  P.above = (uint8_t*)N->mem.alloc(n);
+  P.k_stop = (float*)N->mem.alloc(sizeof(float) * n);
+  P.k_walk = (float*)N->mem.alloc(sizeof(float) * n);
+  P.freq = (float*)N->mem.alloc(sizeof(float) * n);
+  P.ticks = (unsigned int*)N->mem.alloc(sizeof(unsigned int) * n);
+  P.encounters = (int*)N->mem.alloc(sizeof(int) * n);
+  P.drive = (float*)N->mem.alloc(sizeof(float) * 2 * n);
+  if (!N->mem.ok) return -1;
+  if (nmf_navigator_reset(N, nullptr, nullptr) != 0) return -1;
+  HIP_OK(hipDeviceSynchronize());
+  return 0;
+}
+
+extern "C" nmf_navigator* nmf_navigator_create(nmf_batch* b, const nmf_navigator_params* p) {
+  if (!b || !p) { fail("nmf_navigator_create: null batch / params"); return nullptr; }
+  return build_or_destroy(b->mem.device, "nmf_navigator_create", new nmf_navigator(), nmf_navigator_destroy, [&](nmf_navigator* N) {
+    N->n_worlds = b->n_worlds;
+    return fill_navigator(N, b, p);
+  });
+}
+
+extern "C" void* nmf_navigator_field_ptr(nmf_navigator* N, int which, int32_t* width) {
+  if (!N) { fail("nmf_navigator_field_ptr: null navigator"); return nullptr; }
+  const nmf::NavPtrs& P = N->ptrs;
+  void* ptr[9] = {P.state, P.remaining, P.above, P.k_stop, P.k_walk, P.freq, P.ticks, P.encounters, P.drive};
+  if (which < 0 || which > 8) { fail("nmf_navigator_field_ptr: no such field"); return nullptr; }
+  if (width) *width = which == NMF_NAVIGATOR_DRIVE ? 2 : 1;
+  return ptr[which];
+}
+
+// Pure stream-ordered work: one kernel launch.
+extern "C" int nmf_navigator_update(nmf_navigator* N, const float* odor_dev, int n_dims, const float* wind_dev, int wind_rows,
+                                    float* drive_out_dev, void* stream) {
+  if (!N) return fail("nmf_navigator_update: null navigator");
+  if (!odor_dev) return fail("nmf_navigator_update: null odor");
+  if (!wind_dev) return fail("nmf_navigator_update: null wind");
+  if (n_dims <= N->args.p.odor_dim)
+    return fail("nmf_navigator_update: odor has " + std::to_string(n_dims) + " dimensions, the navigator reads dimension " + std::to_string(N->args.p.odor_dim));
+  if (wind_rows != 1 && wind_rows != N->n_worlds)
+    return fail("nmf_navigator_update: wind_rows must be 1 or " + std::to_string(N->n_worlds) + " (n_worlds), got " + std::to_string(wind_rows));
+  if (((uintptr_t)odor_dev & 15) || ((uintptr_t)wind_dev & 3) || ((uintptr_t)drive_out_dev & 7))
+    return fail("nmf_navigator_update: odor must be 16-byte, wind 4-byte and drive 8-byte aligned");
+  DEVICE_GUARD(N);
+  hipLaunchKernelGGL(nmf::nmf_navigator_update_kernel, dim3((unsigned)((N->n_worlds + nmf::kNavThreads - 1) / nmf::kNavThreads)), dim3(nmf::kNavThreads),
+                     0, (hipStream_t)stream, N->args, N->ptrs, odor_dev, n_dims, wind_dev, wind_rows, drive_out_dev ? drive_out_dev : N->ptrs.drive);
   HIP_OK(hipGetLastError());
   return 0;
 }

@@ -30,6 +30,7 @@ typedef struct nmf_cpg nmf_cpg;
 typedef struct nmf_plume nmf_plume;
 typedef struct nmf_odometry nmf_odometry;
 typedef struct nmf_motion nmf_motion;
+typedef struct nmf_navigator nmf_navigator;
 
 /* Per-world fields addressable through nmf_field_ptr / nmf_gather_* */
 enum nmf_field {
@@ -737,6 +738,97 @@ int nmf_motion_update(nmf_motion* motion, const float* omm_dev, const float* bas
 #define NMF_MOTION_DRIVE 6        /* [2] float32: a drive buffer of the handle's own (starts at 1)             */
 #define NMF_MOTION_FRESH 7        /* [1] uint8                                                                 */
 void* nmf_motion_field_ptr(nmf_motion* motion, int which, int32_t* width);
+
+/* Plume navigation with its state on the device (flygym_amd.controllers.PlumeNavigator; csrc/nmf_navigator.hip): a stochastic walk /
+ * stop / turn state machine driven by odor onsets ("encounters"), in the form of Demir et al. 2020 as flygym 1.x steered its
+ * plume-tracking task with it.  No reference counterpart (the snapshot holds no controllers): build-defined and pinned by nothing
+ * (specification tests/navigator_spec.py).
+ * State per world: state (int32: the NMF_NAV_ values below), remaining (int32, ticks left of a turn), above (uint8: the antennal sum
+ * was above the threshold in the last update), the leaky filters k_stop, k_walk and freq (float32), ticks (uint32, updates since
+ * the reset: the noise counter), encounters (int32, cumulative) and drive[2] (float32: left, right, the order of NMF_CPG_DRIVE).
+ * One update (one launch per control tick) reads odor[w][odor_dim][4] (palp L, palp R, antenna L, antenna R: the layout of
+ * nmf_odor_intensity and nmf_plume_sample_sites), the wind (wx, wy) of row w or of the one shared row, and the quaternion
+ * (qw, qx, qy, qz) of root_seg in the batch's seg_xquat as it stands.  Everything is float32, every operation is rounded on its own
+ * (no contraction, no reassociation), and every right-hand side is the old state except that the probabilities use the filters
+ * just updated:
+ *   s = I[2] + I[3];  now = s > threshold (false for a NaN);  e = now and not above;  above <- now;  encounters <- encounters + e
+ *   k_stop <- fl(k_stop decay_stop) + e;  k_walk <- fl(k_walk decay_walk) + e;  freq <- fl(freq decay_freq) + (e ? inv_tau_freq : 0)
+ *   ax = 1 - 2 (qy qy + qz qz),  ay = 2 (qx qy + qw qz)          (the body's x axis in the ground plane, as nmf_odometry_update)
+ *   cross = fl(ay wx) - fl(ax wy)                                (> 0: upwind, the direction -wind, lies to the left; false for a NaN)
+ *   u_m = (hash(seed ^ (first_world + w) 0x9E3779B9 ^ ticks 0x85EBCA6B ^ (8 + m) 0xC2B2AE35) >> 8) 2^-24,  m = 0, 1, 2
+ *         (uint32 arithmetic; the mixer and the key of csrc/nmf_plume.hip, whose wind noise uses the draw indices 0..7)
+ *   c01(x) = x < 0 ? 0 : (x > 1 ? 1 : x)                         (comparisons: a NaN would pass through)
+ *   p_stop = c01(dt (lambda_ws0 + dlambda_ws k_stop)),  p_walk = c01(dt (lambda_sw0 + dlambda_sw k_walk)),  p_turn = c01(dt lambda_turn)
+ *   x = p_up0 + up_gain freq;  p_up = x < p_up_min ? p_up_min : (x > p_up_max ? p_up_max : x)
+ *   a turn (state TURN_LEFT or TURN_RIGHT): remaining <- remaining - 1; when that is <= 0 the state becomes WALK
+ *   WALK: u_0 < p_stop -> STOP;  else u_1 < p_turn -> remaining <- turn_ticks and a turn towards (u_2 < p_up ? upwind : downwind):
+ *         TURN_LEFT when (towards upwind) == (cross > 0), else TURN_RIGHT
+ *   STOP: u_0 < p_walk -> WALK
+ *   ticks <- ticks + 1;  drive <- the row of the NEW state: walk_drive, stop_drive, turn_drive = (inner, outer) with the inner side
+ *         left for TURN_LEFT, swapped for TURN_RIGHT
+ * So a turn holds its drive row for exactly turn_ticks updates.  Nothing is divided and no function is called: decay_x =
+ * exp(-dt / tau_x) and inv_tau_freq = 1 / tau_freq come from the caller, computed in float64 and rounded once to float32, and
+ * turn_ticks = round(turn_duration / dt).  Readings, winds and attitudes that are not finite only ever reach comparisons: the state
+ * stays finite.  A world's noise depends on (seed, first_world + w, ticks) alone: not on the batch it is stepped in. */
+#define NMF_NAV_WALK 0
+#define NMF_NAV_STOP 1
+#define NMF_NAV_TURN_LEFT 2
+#define NMF_NAV_TURN_RIGHT 3
+typedef struct nmf_navigator_params {
+  uint32_t seed;                /* of the noise streams                                                                   */
+  int32_t first_world;          /* global index of world 0 (a shard of a larger population); >= 0                         */
+  int32_t root_seg;             /* index of the body's root segment in the batch's segment order                          */
+  int32_t odor_dim;             /* the odor dimension whose antennae are read (0..7)                                      */
+  int32_t turn_ticks;           /* updates a turn lasts (1..65535)                                                        */
+  float dt;                     /* the control tick in seconds: rates become probabilities per update                     */
+  float threshold;              /* of the antennal sum (>= 0)                                                             */
+  float decay_stop, decay_walk, decay_freq;   /* per update, each in [0, 1]                                              */
+  float inv_tau_freq;           /* what an encounter adds to freq                                                         */
+  float lambda_ws0, dlambda_ws; /* walk -> stop rate per second: the base and its change per unit of k_stop               */
+  float lambda_sw0, dlambda_sw; /* stop -> walk rate likewise, per unit of k_walk                                         */
+  float lambda_turn;            /* turn rate per second while walking                                                     */
+  float p_up0, up_gain, p_up_min, p_up_max;   /* the probability that a turn goes upwind: bounds in [0, 1], min <= max   */
+  float walk_drive[2], stop_drive[2];         /* (left, right)                                                           */
+  float turn_drive[2];          /* (inner, outer)                                                                         */
+} nmf_navigator_params;
+
+/* sizeof(nmf_navigator_params) as this library was compiled (as nmf_eye_params_size). */
+size_t nmf_navigator_params_size(void);
+
+/* An explicit handle for the worlds of `batch`, on its device.  Owns the state arrays and resets every world (nmf_navigator_reset
+ * with a NULL mask).  NOT stream-ordered (allocations); must not be called inside a stream capture.  NULL on error
+ * (nmf_last_error), with nothing left allocated: a parameter that is not finite; a threshold below 0; a decay outside [0, 1];
+ * p_up_min > p_up_max or either outside [0, 1]; turn_ticks outside 1..65535; root_seg outside the batch's segments; odor_dim
+ * outside 0..7; first_world below 0; no device memory.  The handle keeps a pointer to the batch's seg_xquat array: destroy it
+ * before the batch. */
+nmf_navigator* nmf_navigator_create(nmf_batch* batch, const nmf_navigator_params* params);
+void nmf_navigator_destroy(nmf_navigator* navigator);
+
+/* The worlds with mask_dev[w] != 0 (uint8 per world, device memory; NULL: all) get state WALK, remaining 0, above 0, empty
+ * filters, ticks 0 (their noise stream starts again), encounters 0 and walk_drive in the handle's own drive array; the others are
+ * not touched.  Stream-ordered. */
+int nmf_navigator_reset(nmf_navigator* navigator, const uint8_t* mask_dev, void* stream);
+
+/* One update of every world from odor_dev[n_worlds][n_dims][4] float32 (16-byte aligned) and wind_dev[wind_rows][2] float32
+ * (wind_rows = n_worlds, or 1: one row shared by all worlds): argument checks and ONE kernel launch on `stream`, no allocation, no
+ * host synchronisation, hipGraph-capturable (ticks lives on the device, so a captured update draws fresh noise on every replay).
+ * The drive goes to drive_out_dev[n_worlds][2] float32 (8-byte aligned; for example NMF_CPG_DRIVE) or, when that is NULL, to the
+ * handle's own NMF_NAVIGATOR_DRIVE.  Refused: a null handle, odor or wind; n_dims <= odor_dim; wind_rows neither 1 nor n_worlds;
+ * a misaligned buffer. */
+int nmf_navigator_update(nmf_navigator* navigator, const float* odor_dev, int n_dims, const float* wind_dev, int wind_rows,
+                         float* drive_out_dev, void* stream);
+
+/* Device pointer + row width of an array of the handle (zero-copy views; writable between launches). */
+#define NMF_NAVIGATOR_STATE 0       /* [1] int32                                                               */
+#define NMF_NAVIGATOR_REMAINING 1   /* [1] int32                                                               */
+#define NMF_NAVIGATOR_ABOVE 2       /* [1] uint8                                                               */
+#define NMF_NAVIGATOR_K_STOP 3      /* [1] float32                                                             */
+#define NMF_NAVIGATOR_K_WALK 4      /* [1] float32                                                             */
+#define NMF_NAVIGATOR_FREQ 5        /* [1] float32                                                             */
+#define NMF_NAVIGATOR_TICKS 6       /* [1] uint32                                                              */
+#define NMF_NAVIGATOR_ENCOUNTERS 7  /* [1] int32                                                               */
+#define NMF_NAVIGATOR_DRIVE 8       /* [2] float32: the drive buffer of the handle's own (starts at walk_drive)*/
+void* nmf_navigator_field_ptr(nmf_navigator* navigator, int which, int32_t* width);
 
 /* Odor intensity at n_sensors points rigidly attached to named segments (sensor_seg = index into the
  * batch's segment order, sensor_rel = offset in the segment frame): out[w][d][k] = sum_s peak[s][d] / dist^2.
