@@ -39,6 +39,11 @@ sensors once per launch; the oscillators are not changed by them.
 ``PlumeNavigator`` steers the CPG through an intermittent plume: a stochastic walk / stop / turn state machine per world, driven by
 odor onsets and biased upwind, with its state and its noise counter on the device (``csrc/nmf_navigator.hip``; specification
 ``tests/navigator_spec.py``) — the navigator of flygym 1.x's plume-tracking task, build-defined and pinned by nothing.
+
+``HeadStabilizer`` drives the neck from a small network: per world an MLP from the leg joint angles and the leg contact flags to
+the neck's roll and pitch, evaluated in one stateless launch that writes ``ctrl`` (``csrc/nmf_stabilizer.hip``; specification
+``tests/stabilizer_spec.py``) — flygym 1.x's head stabilization, build-defined and pinned by nothing.  The CPGs
+take the leg dofs among a fly's position actuators as their columns, so a fly whose neck is actuated can walk under them.
 """
 
 from __future__ import annotations
@@ -52,14 +57,20 @@ from ._handle import NativeHandle, _field_view, check_params, fly_batch, leg_seg
 from .anatomy import LEGS, JointDOF
 from .replay import MotionSnippet
 
-__all__ = ["TripodCPG", "TurningCPG", "HybridTurningCPG", "SensorySteering", "PlumeNavigator", "navigator_constants"]
+__all__ = ["TripodCPG", "TurningCPG", "HybridTurningCPG", "SensorySteering", "PlumeNavigator", "navigator_constants", "HeadStabilizer", "NECK_DOFS",
+           "LEVELLING_NECK_DOFS"]
 
 TRIPOD_PHASE_BIAS = {"lf": 0.0, "rm": 0.0, "lh": 0.0, "rf": np.pi, "lm": np.pi, "rh": np.pi}
 
 
 class TripodCPG:
     def __init__(self, actuated_dofs: list[JointDOF], timestep: float, *, frequency: float = 12.0, n_phase_bins: int = 256):
-        self.actuated_dofs = list(actuated_dofs)
+        # the columns are the leg dofs of the list: a fly with a neck may carry position actuators on other joints (the head's, for
+        # :class:`HeadStabilizer`), which the walking clip does not drive
+        given = list(actuated_dofs)
+        self.leg_columns = np.array([i for i, d in enumerate(given) if d.child.pos in LEGS], dtype=np.int64)
+        self.n_given = len(given)
+        self.actuated_dofs = [given[i] for i in self.leg_columns]
         self.timestep = float(timestep)
         self.frequency = float(frequency)
         self.n_bins = int(n_phase_bins)
@@ -118,7 +129,7 @@ class TripodCPG:
         holding ``fly`` (``HIPSimulation.model``)."""
         from .compiler.rigid import forward_kinematics
 
-        pos_ids = [i for i, a in enumerate(fly.actuators) if a["kind"] == "position"]
+        pos_ids = [i for i, a in enumerate(fly.actuators) if a["kind"] == "position" and a["jointdof"].child.pos in LEGS]
         if len(pos_ids) != len(self.actuated_dofs):
             raise ValueError("the fly's position actuators do not match the controller's actuated dofs")
         qadr = np.asarray(model["act_trn"])[pos_ids] + 1
@@ -243,6 +254,9 @@ class TurningCPG(NativeHandle, TripodCPG):
             self.adhesion = (float(adhesion[0]), float(adhesion[1]))
             self.stance = self.stance_bins(sim.model, fly, *([float(adhesion[2])] if len(adhesion) == 3 else []))
         self.act_ids = sim.replay_ids(fly_name, with_adhesion=adhesion is not None)
+        if len(self.leg_columns) != self.n_given:        # position actuators off the legs: their ctrl columns are not the table's
+            keep = [*self.leg_columns.tolist(), *range(self.n_given, int(self.act_ids.numel()))]
+            self.act_ids = self.act_ids[sim._torch.as_tensor(keep, device=sim.device)].contiguous()
         n_pos = len(self.actuated_dofs)
         self.n_act = n_pos + (6 if adhesion is not None else 0)
         if int(self.act_ids.numel()) != self.n_act:
@@ -662,3 +676,213 @@ class PlumeNavigator(NativeHandle):
         h = self._handle()
         m = reset_mask(mask, self.n_worlds, self.sim)
         _native.check(_native.lib().nmf_navigator_reset(h, None if m is None else m.data_ptr(), self.sim._stream()))
+
+
+class _StabilizerParams(ctypes.Structure):
+    """``nmf_stabilizer_params`` of include/nmf.h."""
+
+    _fields_ = [("n_q", ctypes.c_int32), ("contacts", ctypes.c_int32), ("n_hidden", ctypes.c_int32), ("hidden", ctypes.c_int32 * 3),
+                ("n_out", ctypes.c_int32), ("thr2", ctypes.c_float * 6), ("lo", ctypes.c_float * 8), ("hi", ctypes.c_float * 8)]
+
+
+NECK_DOFS = ("c_thorax-c_head-roll", "c_thorax-c_head-pitch")
+# The anatomy names a dof after its axis in the child segment's frame, x = yaw, y = pitch, z = roll (``RotationAxis.to_vector``: the
+# legs' convention, z along the limb), and the head's frame is aligned with the thorax's at the neutral pose: forward kinematics
+# shows the neck dof NAMED roll turning the head about the vertical axis and the one named yaw about the forward axis.  The outputs
+# that cancel the thorax's world-frame roll and pitch (``HeadStabilizer.ideal_targets``) therefore belong on these two:
+LEVELLING_NECK_DOFS = ("c_thorax-c_head-yaw", "c_thorax-c_head-pitch")
+
+
+def _leg_contact_flags(torch, sensordata, thr2):
+    """``(n, 6)`` float32 in torch: leg ``l`` touches (``found > 0``) with a squared net force above ``thr2[l]``."""
+    sd = sensordata.reshape(-1, 6, 16)
+    return ((sd[:, :, 0] > 0) & ((sd[:, :, 1:4] ** 2).sum(dim=2) > thr2)).to(torch.float32)
+
+
+class HeadStabilizer(NativeHandle):
+    """Head stabilization on the GPU (``nmf_stabilizer_*``): per world a small MLP from the leg joint angles and the leg contact
+    flags to the neck's roll and pitch that cancel the thorax's rocking, so that the eyes (``EyeRenderer`` hangs its cameras on
+    ``l_eye`` / ``r_eye``) see a steady horizon — the form of flygym 1.x's head-stabilization model.
+
+    Build-defined and pinned by nothing (the reference ships no controllers; nothing is claimed about matching flygym 1.x, and
+    nothing about how much steadier the gaze gets: ``examples/steady_the_gaze.py`` prints what it measures); the statement of the
+    model is include/nmf.h (``nmf_stabilizer_update``), its specification in numpy tests/stabilizer_spec.py.  One :meth:`update`
+    per control tick, from the batch's ``qpos`` and ``sensordata`` as they stand, in float32::
+
+        x[k]       = (qpos[7 + input_dofs[k]] - input_mean[k]) * (1 / input_std[k])
+        x[n_q + l] = leg l touches and |F_l|^2 > contact_force_thr[pair of l]^2 ? 1 : 0        (six flags, unless the threshold is None)
+        h = x;  per layer (W, b):  a = b, then a[j] = fmaf(W[j, k], h[k], a[j]) for k ascending;  h = relu(a), the last layer: y = a
+        out[j] = clip(y[j], limits);  ctrl[actuator of output_dofs[j]] = out[j]                  (with ``drive_actuators``)
+
+    Args:
+        sim: the batch; for a world with several flies ``sim.for_fly(fly_name)``.
+        fly_name: the fly whose joints are read and whose neck is driven.
+        layers: ``[(W, b), ...]`` float32, ``W`` ``(n_out_i, n_in_i)``: one to three hidden layers of 1..64 units and the output
+            layer of 1..8 units; at most 256 inputs.
+        input_dofs: joint dofs (``JointDOF`` or names) read as inputs; default the fly's leg dofs that have position actuators,
+            in ``get_actuated_jointdofs_order("position")`` order (42 on ``make_model``'s flies).
+        input_mean, input_std: per input dof (default 0 and 1): what :meth:`fit` returns.
+        contact_force_thr: per leg pair front / middle / hind, in the contact sensors' force unit — flygym 1.x's values as
+            remembered (its source is not at hand).  ``None`` drops the six flags.
+        output_dofs: the joint dofs the outputs drive; default the neck dofs named roll and pitch (:data:`NECK_DOFS`).  In this
+            anatomy's naming the dof that turns the head about the forward axis — what cancels a world-frame roll — is the one
+            named yaw: a network trained on :meth:`ideal_targets` takes ``output_dofs=LEVELLING_NECK_DOFS`` (see there).
+        limits: ``(lo, hi)``, scalars or one value per output.
+        drive_actuators: write the outputs into the ``ctrl`` columns of the output dofs' position actuators.  ``False`` only
+            fills ``out`` — usable on any skeleton, LEGS_ONLY included.
+
+    ``output`` ``(n_worlds, n_out)`` float32 is the zero-copy view of the handle's own array.  :meth:`update` is one launch of
+    stream-ordered device work on the simulation's stream and can be captured in a graph (with ``cpg.step``: the CPGs leave the
+    neck's ``ctrl`` columns alone).  Close the stabilizer before its simulation.
+    """
+
+    _destroy_entry, _noun, _views = "nmf_stabilizer_destroy", "stabilizer", ("output",)
+
+    def __init__(self, sim, fly_name: str, layers, *, input_dofs=None, input_mean=None, input_std=None,
+                 contact_force_thr=(0.5, 1.0, 3.0), output_dofs=None, limits=(-np.pi / 2, np.pi / 2), drive_actuators: bool = True):
+        sim = fly_batch(sim, fly_name, resolve=False)
+        if fly_name not in sim.world.fly_lookup:
+            raise ValueError(f"no fly named {fly_name!r} in this simulation ({', '.join(sim.world.fly_lookup)})")
+        fly = sim.world.fly_lookup[fly_name]
+        self.sim, self.fly_name, self.n_worlds = sim, fly_name, int(sim.n_worlds)
+        self.layers = [(np.ascontiguousarray(W, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)) for W, b in layers]
+        if not 2 <= len(self.layers) <= 4:
+            raise ValueError(f"layers takes one to three hidden layers and the output layer, got {len(self.layers)} layers")
+        all_dofs = [d.name for d in fly.get_jointdofs_order()]
+        name_of = lambda d: d if isinstance(d, str) else d.name
+        if input_dofs is None:
+            input_dofs = [d for d in fly.get_actuated_jointdofs_order("position") if d.child.pos in LEGS]
+        self.input_dofs = [name_of(d) for d in input_dofs]
+        missing = [d for d in self.input_dofs if d not in all_dofs]
+        if missing:
+            raise ValueError(f"the fly has no joint dof {missing[0]!r}")
+        self._dof = np.array([all_dofs.index(d) for d in self.input_dofs], dtype=np.int32)
+        n_q = len(self.input_dofs)
+        self.contacts = contact_force_thr is not None
+        if self.contacts and len(contact_force_thr) != 3:
+            raise ValueError(f"contact_force_thr takes three values (front, middle, hind legs) or None, got {contact_force_thr!r}")
+        self.n_in, self.n_out = n_q + (6 if self.contacts else 0), int(self.layers[-1][0].shape[0]) if self.layers[-1][0].ndim == 2 else 0
+        n_prev = self.n_in
+        for i, (W, b) in enumerate(self.layers):
+            if W.ndim != 2 or W.shape[1] != n_prev or b.shape != (W.shape[0],):
+                raise ValueError(f"layer {i} must be (W (n, {n_prev}), b (n,)), got {tuple(W.shape)} and {tuple(b.shape)}")
+            n_prev = int(W.shape[0])
+        self._mean = np.zeros(n_q, dtype=np.float32) if input_mean is None else np.ascontiguousarray(input_mean, dtype=np.float32)
+        std = np.ones(n_q, dtype=np.float32) if input_std is None else np.ascontiguousarray(input_std, dtype=np.float32)
+        if self._mean.shape != (n_q,) or std.shape != (n_q,):
+            raise ValueError(f"input_mean and input_std take one value per input dof ({n_q}), got {self._mean.shape} and {std.shape}")
+        if not (std > 0).all():
+            raise ValueError("input_std must be positive")
+        self._inv_std = (1.0 / std.astype(np.float64)).astype(np.float32)       # divided in float64, rounded once
+        bound = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float32), (self.n_out,)))
+        if len(limits) != 2:
+            raise ValueError(f"limits takes (lo, hi), got {limits!r}")
+        self.lo, self.hi = bound(limits[0]), bound(limits[1])
+        self._act = None
+        if drive_actuators:
+            self.output_dofs = [name_of(d) for d in (NECK_DOFS if output_dofs is None else output_dofs)]
+            if len(self.output_dofs) != self.n_out:
+                raise ValueError(f"the network has {self.n_out} outputs for {len(self.output_dofs)} output dofs")
+            ids = {a["jointdof"].name: i for i, a in enumerate(fly.actuators) if a["kind"] == "position"}
+            for d in self.output_dofs:
+                if d not in ids:
+                    raise ValueError(f"{d} has no position actuator to drive: on a skeleton with a neck (ALL_BIOLOGICAL, ALL_POSSIBLE) add "
+                                     f"one with fly.add_actuators([JointDOF.from_name({d!r})], \"position\", kp=...) before the world is "
+                                     "compiled, or pass drive_actuators=False to only fill `out`")
+            self._act = np.array([ids[d] for d in self.output_dofs], dtype=np.int32)
+        else:
+            self.output_dofs = None if output_dofs is None else [name_of(d) for d in output_dofs]
+        check_params(_StabilizerParams, "nmf_stabilizer_params_size", "controllers.py")
+        thr = [float(contact_force_thr["fmh".index(leg[1])]) for leg in LEGS] if self.contacts else [0.0] * 6
+        self.thr2 = np.array([t * t for t in thr], dtype=np.float32)
+        widths = [int(W.shape[0]) for W, _ in self.layers[:-1]]
+        pad = lambda a, n: [*a, *([0] * (n - len(a)))]
+        self._params = _StabilizerParams(n_q, int(self.contacts), len(widths), (ctypes.c_int32 * 3)(*pad(widths[:3], 3)), self.n_out,
+                                         (ctypes.c_float * 6)(*self.thr2.tolist()), (ctypes.c_float * 8)(*pad(self.lo.tolist()[:8], 8)),
+                                         (ctypes.c_float * 8)(*pad(self.hi.tolist()[:8], 8)))
+        self._weights = np.concatenate([a.ravel() for W, b in self.layers for a in (W, b)]).astype(np.float32)
+        h = self._create("nmf_stabilizer_create", sim._batch_h, ctypes.byref(self._params), self._dof.ctypes.data, self._mean.ctypes.data,
+                         self._inv_std.ctypes.data, self._weights.ctypes.data, None if self._act is None else self._act.ctypes.data)
+        self.output = _field_view(sim, _native.lib().nmf_stabilizer_field_ptr, h, 0)
+
+    def update(self, out=None):
+        """One update of every world from the batch's ``qpos`` and ``sensordata`` as they stand.  One kernel launch, no allocation
+        — capturable.  Writes the outputs into ``out`` (``(n_worlds, n_out)`` float32, contiguous, on the simulation's device) or
+        into :attr:`output`, and with ``drive_actuators`` into ``ctrl``; returns the tensor it wrote."""
+        h = self._handle()
+        t = self.sim._torch
+        if out is not None and (not isinstance(out, t.Tensor) or tuple(out.shape) != (self.n_worlds, self.n_out) or out.dtype != t.float32
+                                or out.device != t.device(self.sim.device) or not out.is_contiguous()):
+            got = f"{tuple(out.shape)} {out.dtype} on {out.device}" if isinstance(out, t.Tensor) else type(out).__name__
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {(self.n_worlds, self.n_out)} on {self.sim.device}, got {got}")
+        _native.check(_native.lib().nmf_stabilizer_update(h, None if out is None else out.data_ptr(), self.sim._stream()))
+        return self.output if out is None else out
+
+    # ---- in torch, not bit-pinned: what the network is trained on
+    @staticmethod
+    def collect_inputs(sim, fly_name: str, input_dofs=None, contact_force_thr=(0.5, 1.0, 3.0)):
+        """``(n_worlds, n_in)`` float32 on the simulation's device: the raw (not standardised) joint angles of ``input_dofs`` and,
+        unless the threshold is None, the six contact flags — the inputs a :class:`HeadStabilizer` with these arguments reads,
+        for :meth:`fit`."""
+        sim = fly_batch(sim, fly_name, resolve=False)
+        fly, t = sim.world.fly_lookup[fly_name], sim._torch
+        if input_dofs is None:
+            input_dofs = [d for d in fly.get_actuated_jointdofs_order("position") if d.child.pos in LEGS]
+        all_dofs = [d.name for d in fly.get_jointdofs_order()]
+        cols = t.as_tensor([7 + all_dofs.index(d if isinstance(d, str) else d.name) for d in input_dofs], device=sim.device)
+        x = sim.field("qpos")[:, cols]
+        if contact_force_thr is None:
+            return x
+        thr2 = t.as_tensor([float(contact_force_thr["fmh".index(leg[1])]) ** 2 for leg in LEGS], dtype=t.float32, device=sim.device)
+        return t.cat([x, _leg_contact_flags(t, sim.field("sensordata"), thr2)], dim=1)
+
+    @staticmethod
+    def ideal_targets(root_quat):
+        """``(..., 2)``: minus the thorax's roll and pitch (x-y-z Tait–Bryan angles of ``(..., 4)`` quaternions ``(w, x, y, z)``, a
+        torch tensor on any device) — the neck angles that would keep the head level, the signal flygym 1.x trained against."""
+        import torch
+
+        w, x, y, z = root_quat.unbind(dim=-1)
+        roll = torch.atan2(2 * (w * x + y * z), 1 - 2 * (x * x + y * y))
+        pitch = torch.asin(torch.clamp(2 * (w * y - z * x), -1.0, 1.0))
+        return torch.stack([-roll, -pitch], dim=-1)
+
+    @staticmethod
+    def fit(inputs, targets, hidden=(32, 32), *, epochs: int = 300, lr: float = 1e-2, n_flags: int = 6, seed: int = 0):
+        """Train the MLP ``n_in -> hidden... -> n_out`` (ReLU; the default 32, 32 is flygym 1.x's three-layer network as remembered)
+        on ``inputs`` ``(N, n_in)`` (the last ``n_flags`` columns are contact flags) against ``targets`` ``(N, n_out)``: full-batch
+        Adam on the mean squared error, float32, on the CPU, deterministic for a given seed.  Only the joint columns are
+        standardised.  Returns ``(layers, mean, std)`` for :class:`HeadStabilizer` — measured on some flies, used on others, as
+        ``PathIntegrator.calibrate``."""
+        import torch
+
+        X = torch.as_tensor(inputs).detach().to("cpu", torch.float32)
+        Y = torch.as_tensor(targets).detach().to("cpu", torch.float32)
+        if X.ndim != 2 or Y.ndim != 2 or X.shape[0] != Y.shape[0] or X.shape[0] < 2 or not 0 <= int(n_flags) < X.shape[1]:
+            raise ValueError(f"fit takes inputs (N, n_in) and targets (N, n_out) with N >= 2, got {tuple(X.shape)} and {tuple(Y.shape)}")
+        n_q = X.shape[1] - int(n_flags)
+        mean = X[:, :n_q].mean(dim=0)
+        std = X[:, :n_q].std(dim=0).clamp_min(1e-6)
+        Z = torch.cat([(X[:, :n_q] - mean) / std, X[:, n_q:]], dim=1)
+        gen = torch.Generator().manual_seed(int(seed))
+        sizes = [Z.shape[1], *[int(h) for h in hidden], Y.shape[1]]
+        params = []
+        for a, b in zip(sizes[:-1], sizes[1:]):
+            W = (torch.rand((b, a), generator=gen) * 2 - 1) * (6.0 / (a + b)) ** 0.5
+            params += [W.requires_grad_(), torch.zeros(b, requires_grad=True)]
+
+        def forward(h):
+            for i in range(0, len(params), 2):
+                h = torch.nn.functional.linear(h, params[i], params[i + 1])
+                if i + 2 < len(params):
+                    h = torch.relu(h)
+            return h
+
+        opt = torch.optim.Adam(params, lr=float(lr))
+        for _ in range(int(epochs)):
+            opt.zero_grad()
+            loss = ((forward(Z) - Y) ** 2).mean()
+            loss.backward()
+            opt.step()
+        layers = [(params[i].detach().numpy().copy(), params[i + 1].detach().numpy().copy()) for i in range(0, len(params), 2)]
+        return layers, mean.numpy().copy(), std.numpy().copy()

@@ -20,9 +20,9 @@
 #include "nmf_step.hip"
 #include "nmf_sensors.hip"
 // `#pragma clang fp reassociate(off)` at file scope holds from the first file that sets it to the end of the translation unit:
-// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip, nmf_plume.hip, nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip, nmf_navigator.hip and the host code
+// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip, nmf_plume.hip, nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip, nmf_navigator.hip, nmf_stabilizer.hip and the host code
 // below are all compiled under it, and the files above are not.  Which files it covers decides their kernels' arithmetic: keep the
-// order (nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip and nmf_navigator.hip add pragmas inside their functions only: nothing of them reaches past the file).
+// order (nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip, nmf_navigator.hip and nmf_stabilizer.hip add pragmas inside their functions only: nothing of them reaches past the file).
 #include "nmf_eyes.hip"
 #include "nmf_camera.hip"
 #include "nmf_replay.hip"
@@ -32,6 +32,7 @@
 #include "nmf_odometry.hip"
 #include "nmf_motion.hip"
 #include "nmf_navigator.hip"
+#include "nmf_stabilizer.hip"
 #include "nmf_skeleton.h"      // nmf_model, the blob parser, classify_skeleton
 #endif
 
@@ -64,7 +65,7 @@ struct DeviceGuard {
   DeviceGuard guard_((b)->mem.device);                                                        \
   if (guard_.err != hipSuccess) return fail(std::string("hipSetDevice: ") + hipGetErrorString(guard_.err))
 
-// The device memory of one handle (batch, eye plan, camera plan, CPG, plume, odometry, motion, navigator): every allocation is 16-byte granular, recorded, and freed
+// The device memory of one handle (batch, eye plan, camera plan, CPG, plume, odometry, motion, navigator, stabilizer): every allocation is 16-byte granular, recorded, and freed
 // with the handle.  The first failure sets the error text, named after the entry point `who`, and sticks: later calls return
 // null without touching the device, so that a caller tests `ok` once after its last allocation.
 struct DevMem {
@@ -1839,6 +1840,132 @@ extern "C" int nmf_navigator_update(nmf_navigator* N, const float* odor_dev, int
   DEVICE_GUARD(N);
   hipLaunchKernelGGL(nmf::nmf_navigator_update_kernel, dim3((unsigned)((N->n_worlds + nmf::kNavThreads - 1) / nmf::kNavThreads)), dim3(nmf::kNavThreads),
                      0, (hipStream_t)stream, N->args, N->ptrs, odor_dev, n_dims, wind_dev, wind_rows, drive_out_dev ? drive_out_dev : N->ptrs.drive);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// ---- head stabilization (nmf_stabilizer.hip) ----
+// The uploaded network and the handle's own output array; the batch lends its qpos, sensordata and ctrl arrays to every update.
+struct nmf_stabilizer {
+  int n_worlds = 0;
+  nmf::StabArgs args{};
+  const float* qpos = nullptr; const float* sensordata = nullptr; float* ctrl = nullptr;
+  const int* dof = nullptr; const float* mean = nullptr; const float* inv_std = nullptr; const float* blob = nullptr;
+  float* out = nullptr;
+  unsigned lds_bytes = 0;
+  DevMem mem;
+};
+
+extern "C" size_t nmf_stabilizer_params_size(void) { return sizeof(nmf_stabilizer_params); }
+
+extern "C" void nmf_stabilizer_destroy(nmf_stabilizer* S) {
+  if (!S) return;
+  S->mem.release();
+  delete S;
+}
+
+static int fill_stabilizer(nmf_stabilizer* S, const nmf_batch* b, const nmf_stabilizer_params* p, const int32_t* dof, const float* mean,
+                           const float* inv_std, const float* weights, const int32_t* act) {
+  const std::string who = "nmf_stabilizer_create: ";
+  if (p->n_hidden < 1 || p->n_hidden > NMF_STABILIZER_MAX_HIDDEN)
+    return fail(who + "n_hidden must be in 1..3, got " + std::to_string(p->n_hidden));
+  for (int i = 0; i < p->n_hidden; ++i)
+    if (p->hidden[i] < 1 || p->hidden[i] > NMF_STABILIZER_MAX_WIDTH)
+      return fail(who + "hidden[" + std::to_string(i) + "] must be in 1..64, got " + std::to_string(p->hidden[i]));
+  if (p->n_q < 1) return fail(who + "n_q must be at least 1, got " + std::to_string(p->n_q));
+  const int n_in = p->n_q + (p->contacts ? 6 : 0);
+  if (p->n_q > NMF_STABILIZER_MAX_IN || n_in > NMF_STABILIZER_MAX_IN) return fail(who + "n_in must be at most 256, got " + std::to_string(n_in));
+  if (p->n_out < 1 || p->n_out > NMF_STABILIZER_MAX_OUT) return fail(who + "n_out must be in 1..8, got " + std::to_string(p->n_out));
+  const int n_dof = b->model->nq - 7, nu = b->model->nu;
+  for (int k = 0; k < p->n_q; ++k)
+    if (dof[k] < 0 || dof[k] >= n_dof)
+      return fail(who + "dof[" + std::to_string(k) + "] = " + std::to_string(dof[k]) + " is outside the model's " + std::to_string(n_dof) + " joint dofs");
+  for (int j = 0; act && j < p->n_out; ++j)
+    if (act[j] < 0 || act[j] >= nu)
+      return fail(who + "act[" + std::to_string(j) + "] = " + std::to_string(act[j]) + " is outside the model's " + std::to_string(nu) + " controls (nu)");
+  for (int j = 0; j < p->n_out; ++j) {
+    if (!std::isfinite(p->lo[j]) || !std::isfinite(p->hi[j])) return fail(who + "a bound is not finite");
+    if (p->lo[j] > p->hi[j]) return fail(who + "lo[" + std::to_string(j) + "] > hi[" + std::to_string(j) + "]");
+  }
+  for (int k = 0; k < p->n_q; ++k)
+    if (!std::isfinite(mean[k]) || !std::isfinite(inv_std[k])) return fail(who + "mean or inv_std is not finite at input " + std::to_string(k));
+  if (p->contacts) {
+    for (int l = 0; l < 6; ++l)
+      if (!std::isfinite(p->thr2[l])) return fail(who + "thr2 is not finite at leg " + std::to_string(l));
+    if (b->model->nsensor == 0 || !b->st.sensordata || b->widths[NMF_SENSORDATA] != 96)
+      return fail(who + "the contact flags need six leg sensors of 16 values, the batch's sensordata is " + std::to_string(b->widths[NMF_SENSORDATA]) + " wide");
+  }
+  nmf::StabArgs& A = S->args;
+  A.n_worlds = S->n_worlds; A.qpos_stride = b->widths[NMF_QPOS]; A.sens_stride = b->widths[NMF_SENSORDATA]; A.ctrl_stride = b->widths[NMF_CTRL];
+  A.n_q = p->n_q; A.n_in = n_in; A.contacts = p->contacts ? 1 : 0; A.n_layers = p->n_hidden + 1; A.drive = act ? 1 : 0;
+  // the blob: per layer bias[jpad], then Wt[k][jpad], jpad = the width rounded up to a block, zeros in the padding
+  std::vector<float> blob;
+  const float* src = weights;
+  int n_prev = n_in;
+  for (int i = 0; i < A.n_layers; ++i) {
+    const int width = i < p->n_hidden ? p->hidden[i] : p->n_out;
+    const int jpad = (width + nmf::kStabBlock - 1) / nmf::kStabBlock * nmf::kStabBlock;
+    const size_t count = (size_t)width * (size_t)n_prev + (size_t)width;
+    for (size_t c = 0; c < count; ++c)
+      if (!std::isfinite(src[c])) return fail(who + "a weight or bias of layer " + std::to_string(i) + " is not finite");
+    A.width[i] = width; A.offset[i] = (int)blob.size();
+    blob.resize(blob.size() + (size_t)jpad * (size_t)(n_prev + 1), 0.f);
+    float* bias = blob.data() + A.offset[i];
+    float* wt = bias + jpad;
+    for (int j = 0; j < width; ++j) {
+      bias[j] = src[(size_t)width * (size_t)n_prev + j];
+      for (int k = 0; k < n_prev; ++k) wt[(size_t)k * jpad + j] = src[(size_t)j * n_prev + k];
+    }
+    src += count;
+    n_prev = width;
+  }
+  // two LDS buffers of [unit][lane]: the inputs and the second hidden layer in the first, the other hidden layers in the second
+  const int size_a = std::max(n_in, p->n_hidden >= 2 ? p->hidden[1] : 0);
+  const int size_b = std::max(p->hidden[0], p->n_hidden >= 3 ? p->hidden[2] : 0);
+  A.lds_b = size_a;
+  S->lds_bytes = (unsigned)(sizeof(float) * nmf::kStabLanes * (size_t)(size_a + size_b));
+  if (S->lds_bytes > 64u * 1024u)
+    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&nmf::nmf_stabilizer_update_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)(sizeof(float) * nmf::kStabLanes * (NMF_STABILIZER_MAX_IN + NMF_STABILIZER_MAX_WIDTH))));
+  for (int j = 0; j < NMF_STABILIZER_MAX_OUT; ++j) {
+    const bool used = j < p->n_out;
+    A.lo[j] = used ? p->lo[j] : 0.f; A.hi[j] = used ? p->hi[j] : 0.f; A.act[j] = used && act ? act[j] : 0;
+  }
+  for (int l = 0; l < 6; ++l) A.thr2[l] = p->contacts ? p->thr2[l] : 0.f;
+  S->qpos = b->st.qpos; S->sensordata = b->st.sensordata; S->ctrl = b->st.ctrl;
+  S->dof = (const int*)S->mem.upload(dof, sizeof(int) * (size_t)p->n_q);
+  S->mean = (const float*)S->mem.upload(mean, sizeof(float) * (size_t)p->n_q);
+  S->inv_std = (const float*)S->mem.upload(inv_std, sizeof(float) * (size_t)p->n_q);
+  S->blob = (const float*)S->mem.upload(blob.data(), sizeof(float) * blob.size());
+  S->out = (float*)S->mem.alloc(sizeof(float) * (size_t)S->n_worlds * (size_t)p->n_out);
+  if (!S->mem.ok) return -1;
+  return 0;
+}
+
+extern "C" nmf_stabilizer* nmf_stabilizer_create(nmf_batch* b, const nmf_stabilizer_params* p, const int32_t* dof, const float* mean,
+                                                 const float* inv_std, const float* weights, const int32_t* act) {
+  if (!b || !p || !dof || !mean || !inv_std || !weights) { fail("nmf_stabilizer_create: null batch / params / dof / mean / inv_std / weights"); return nullptr; }
+  return build_or_destroy(b->mem.device, "nmf_stabilizer_create", new nmf_stabilizer(), nmf_stabilizer_destroy, [&](nmf_stabilizer* S) {
+    S->n_worlds = b->n_worlds;
+    return fill_stabilizer(S, b, p, dof, mean, inv_std, weights, act);
+  });
+}
+
+extern "C" void* nmf_stabilizer_field_ptr(nmf_stabilizer* S, int which, int32_t* width) {
+  if (!S) { fail("nmf_stabilizer_field_ptr: null stabilizer"); return nullptr; }
+  if (which != NMF_STABILIZER_OUTPUT) { fail("nmf_stabilizer_field_ptr: no such field"); return nullptr; }
+  if (width) *width = S->args.width[S->args.n_layers - 1];
+  return S->out;
+}
+
+// Pure stream-ordered work: one kernel launch.
+extern "C" int nmf_stabilizer_update(nmf_stabilizer* S, float* out_dev, void* stream) {
+  if (!S) return fail("nmf_stabilizer_update: null stabilizer");
+  if ((uintptr_t)out_dev & 15) return fail("nmf_stabilizer_update: out must be 16-byte aligned");
+  DEVICE_GUARD(S);
+  hipLaunchKernelGGL(nmf::nmf_stabilizer_update_kernel, dim3((unsigned)((S->n_worlds + nmf::kStabLanes - 1) / nmf::kStabLanes)), dim3(nmf::kStabLanes * nmf::kStabWaves),
+                     S->lds_bytes, (hipStream_t)stream, S->args, S->qpos, S->sensordata, S->dof, S->mean, S->inv_std, S->blob, S->ctrl,
+                     out_dev ? out_dev : S->out);
   HIP_OK(hipGetLastError());
   return 0;
 }

@@ -31,6 +31,7 @@ typedef struct nmf_plume nmf_plume;
 typedef struct nmf_odometry nmf_odometry;
 typedef struct nmf_motion nmf_motion;
 typedef struct nmf_navigator nmf_navigator;
+typedef struct nmf_stabilizer nmf_stabilizer;
 
 /* Per-world fields addressable through nmf_field_ptr / nmf_gather_* */
 enum nmf_field {
@@ -829,6 +830,64 @@ int nmf_navigator_update(nmf_navigator* navigator, const float* odor_dev, int n_
 #define NMF_NAVIGATOR_ENCOUNTERS 7  /* [1] int32                                                               */
 #define NMF_NAVIGATOR_DRIVE 8       /* [2] float32: the drive buffer of the handle's own (starts at walk_drive)*/
 void* nmf_navigator_field_ptr(nmf_navigator* navigator, int which, int32_t* width);
+
+/* Head stabilization: a small network drives the neck (flygym_amd.controllers.HeadStabilizer; csrc/nmf_stabilizer.hip), in the form
+ * of flygym 1.x's head-stabilization model: an MLP from the leg joint angles and the leg contact flags to the neck's roll and pitch
+ * that cancel the thorax's rocking.  No reference counterpart (the snapshot holds no controllers): build-defined and pinned by
+ * nothing (specification tests/stabilizer_spec.py).  The primitive is a per-world MLP evaluated in one launch.
+ * Stateless.  One update (one launch per control tick) reads the batch's qpos and sensordata as they stand and, per world w, in
+ * float32:
+ *   x[k]       = fl(fl(qpos[w][7 + dof[k]] - mean[k]) inv_std[k])                 k < n_q   (two roundings; nothing is divided)
+ *   m_l        = fmaf(Fz, Fz, fmaf(Fy, Fy, fl(Fx Fx)))                            F = sensordata[w][16 l + 1 .. 3], leg l's net force
+ *   x[n_q + l] = (sensordata[w][16 l] > 0 and m_l > thr2[l]) ? 1 : 0              l < 6, when contacts != 0: n_in = n_q + 6, else n_q
+ *   h_0 = x;  layer i = 0 .. n_hidden:  a[j] = b_i[j];  for k ascending: a[j] = fmaf(W_i[j][k], h_{i-1}[k], a[j])
+ *             a hidden layer: h_i[j] = a[j] > 0 ? a[j] : 0;   the last layer: y[j] = a[j]
+ *   y[j]       = y[j] < lo[j] ? lo[j] : (y[j] > hi[j] ? hi[j] : y[j])             (comparisons)
+ *   out[w][j]  = y[j];  and, when the handle has actuator ids:  ctrl[w][act[j]] = y[j]
+ * fmaf is the fused multiply-add: one rounding per step of a chain that starts at the bias and runs over the inputs in ascending
+ * order.  That order is the specification; how the work is split over lanes is not.  thr2 is the squared force threshold, mean
+ * and inv_std = 1 / std come from the caller.  Values of qpos and sensordata that are not finite are outside the contract: they
+ * index nothing, and nothing is said about the results' bits. */
+#define NMF_STABILIZER_MAX_HIDDEN 3      /* hidden layers                                    */
+#define NMF_STABILIZER_MAX_WIDTH 64      /* units of a hidden layer                          */
+#define NMF_STABILIZER_MAX_IN 256        /* n_in                                             */
+#define NMF_STABILIZER_MAX_OUT 8         /* n_out                                            */
+typedef struct nmf_stabilizer_params {
+  int32_t n_q;                  /* joint angles read (>= 1)                                                               */
+  int32_t contacts;             /* != 0: the six contact flags follow the joint angles                                    */
+  int32_t n_hidden;             /* hidden layers (1..3)                                                                   */
+  int32_t hidden[3];            /* their widths (1..64 each); entries past n_hidden are ignored                           */
+  int32_t n_out;                /* outputs (1..8)                                                                         */
+  float thr2[6];                /* squared contact-force threshold per leg (legs in LEGS order); read when contacts != 0  */
+  float lo[8], hi[8];           /* the outputs' bounds, lo[j] <= hi[j]; entries past n_out are ignored                    */
+} nmf_stabilizer_params;
+
+/* sizeof(nmf_stabilizer_params) as this library was compiled (as nmf_eye_params_size). */
+size_t nmf_stabilizer_params_size(void);
+
+/* An explicit handle for the worlds of `batch`, on its device.  Host arrays, copied: dof[n_q] int32 (joint dof indices: qpos
+ * column 7 + dof[k]; repeats are allowed), mean[n_q] and inv_std[n_q] float32, `weights` float32 = W_0 (row-major
+ * [hidden[0]][n_in]), b_0, W_1, b_1, ... up to the output layer's W ([n_out][width of the last hidden layer]) and b, and
+ * act[n_out] int32 (control ids that receive the outputs) or NULL (the update only fills `out`).  Owns the uploaded network and
+ * the (n_worlds, n_out) output array.  NOT stream-ordered (allocations); must not be called inside a stream capture.  NULL on error
+ * (nmf_last_error), with nothing left allocated: n_hidden outside 1..3; a hidden width outside 1..64; n_q < 1; n_in > 256;
+ * n_out outside 1..8; a dof[k] outside the model's joint dofs (0 .. nq - 8); an act[j] outside 0 .. nu - 1; lo[j] > hi[j]; a
+ * weight, bias, mean, inv_std, thr2 or bound that is not finite; contacts on a batch whose sensordata is not six leg sensors of 16
+ * values; a null batch, params, dof, mean, inv_std or weights; no device memory.  The handle keeps pointers to the batch's qpos,
+ * sensordata and ctrl arrays: destroy it before the batch. */
+nmf_stabilizer* nmf_stabilizer_create(nmf_batch* batch, const nmf_stabilizer_params* params, const int32_t* dof, const float* mean,
+                                      const float* inv_std, const float* weights, const int32_t* act);
+void nmf_stabilizer_destroy(nmf_stabilizer* stabilizer);
+
+/* One update of every world: argument checks and ONE kernel launch on `stream`, no allocation, no host synchronisation,
+ * hipGraph-capturable.  The outputs go to out_dev[n_worlds][n_out] float32 (16-byte aligned) or, when that is NULL, to the
+ * handle's own NMF_STABILIZER_OUTPUT; with actuator ids they also go into the batch's ctrl.  No other device memory is written.
+ * Refused: a null handle; a misaligned out_dev. */
+int nmf_stabilizer_update(nmf_stabilizer* stabilizer, float* out_dev, void* stream);
+
+/* Device pointer + row width of an array of the handle (zero-copy view; writable between launches). */
+#define NMF_STABILIZER_OUTPUT 0     /* [n_out] float32: the output array of the handle's own (starts at 0)     */
+void* nmf_stabilizer_field_ptr(nmf_stabilizer* stabilizer, int which, int32_t* width);
 
 /* Odor intensity at n_sensors points rigidly attached to named segments (sensor_seg = index into the
  * batch's segment order, sensor_rel = offset in the segment frame): out[w][d][k] = sum_s peak[s][d] / dist^2.
