@@ -207,6 +207,12 @@ def lib():
             "nmf_stabilizer_destroy": (None, [vp]),
             "nmf_stabilizer_update": (ci, [vp, vp, vp]),
             "nmf_stabilizer_field_ptr": (vp, [vp, ci, ctypes.POINTER(ctypes.c_int32)]),
+            "nmf_rules_params_size": (ctypes.c_size_t, []),
+            "nmf_rules_create": (vp, [vp, vp, vp, vp, vp, vp, vp]),
+            "nmf_rules_destroy": (None, [vp]),
+            "nmf_rules_reset": (ci, [vp, vp, vp]),
+            "nmf_rules_field_ptr": (vp, [vp, ci, ctypes.POINTER(ctypes.c_int32)]),
+            "nmf_rules_advance": (ci, [vp, ci, vp, ci, vp]),
             "nmf_odor_intensity": (ci, [vp, vp, vp, ci, vp, vp, ci, ci, vp, vp]),
             "nmf_replay_resample": (ci, [vp, ci, ci, ctypes.c_double, ctypes.c_double, vp, ci, ci, vp, vp]),
         }

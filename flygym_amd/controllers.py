@@ -32,6 +32,11 @@ remembered): a leg that hangs much lower than the others (it step
 while it swings (it hit a wall) are lifted by a correction added to their targets.  The rules read the batch's pose and contact
 sensors once per launch; the oscillators are not changed by them.
 
+``RuleBasedController`` is flygym 1.x's third walking controller, the decentralised one: no oscillators, every leg starts a step
+when Cruse's rules 1 to 3 — scored from the other legs' step counters — say so, and the gait follows from the weights
+(``csrc/nmf_rules.hip``; specification ``tests/rules_spec.py``; build-defined and pinned by nothing).  It takes the
+same drive and writes the same table as ``TurningCPG``.
+
 ``SensorySteering`` closes the loop from the senses: one stateless launch (``csrc/nmf_taxis.hip``; specification
 ``tests/taxis_spec.py``) turns the ommatidia readings of both eyes and the readings of the four odor sites into the drive of a
 ``TurningCPG`` — flygym 1.x's visual taxis and odor taxis, build-defined and pinned by nothing.
@@ -57,7 +62,7 @@ from ._handle import NativeHandle, _field_view, check_params, fly_batch, leg_seg
 from .anatomy import LEGS, JointDOF
 from .replay import MotionSnippet
 
-__all__ = ["TripodCPG", "TurningCPG", "HybridTurningCPG", "SensorySteering", "PlumeNavigator", "navigator_constants", "HeadStabilizer", "NECK_DOFS",
+__all__ = ["TripodCPG", "TurningCPG", "HybridTurningCPG", "RuleBasedController", "rule_matrices", "swing_runs", "SensorySteering", "PlumeNavigator", "navigator_constants", "HeadStabilizer", "NECK_DOFS",
            "LEVELLING_NECK_DOFS"]
 
 TRIPOD_PHASE_BIAS = {"lf": 0.0, "rm": 0.0, "lh": 0.0, "rf": np.pi, "lm": np.pi, "rh": np.pi}
@@ -210,6 +215,19 @@ class _CpgParams(ctypes.Structure):
                 ("adhesion_off", ctypes.c_float), ("table_steps", ctypes.c_int32)]
 
 
+def _table_columns(cpg: TripodCPG, sim, fly_name: str, with_adhesion: bool):
+    """``(act_ids, n_act)`` of the table a controller built on ``cpg`` writes for ``fly_name``: the ctrl ids of its leg columns (and
+    of the six adhesion columns) and their number."""
+    act_ids = sim.replay_ids(fly_name, with_adhesion=with_adhesion)
+    if len(cpg.leg_columns) != cpg.n_given:              # position actuators off the legs: their ctrl columns are not the table's
+        keep = [*cpg.leg_columns.tolist(), *range(cpg.n_given, int(act_ids.numel()))]
+        act_ids = act_ids[sim._torch.as_tensor(keep, device=sim.device)].contiguous()
+    n_act = len(cpg.actuated_dofs) + (6 if with_adhesion else 0)
+    if int(act_ids.numel()) != n_act:
+        raise ValueError(f"the fly has {int(act_ids.numel())} actuators for a table of {n_act} columns")
+    return act_ids, n_act
+
+
 class TurningCPG(NativeHandle, TripodCPG):
     """Closed-loop tripod CPG of one fly of a :class:`~flygym_amd.HIPSimulation`, advanced on the GPU (``nmf_cpg_advance``).
 
@@ -253,14 +271,8 @@ class TurningCPG(NativeHandle, TripodCPG):
                 raise ValueError(f"adhesion must be (on, off) or (on, off, threshold), got {adhesion!r}")
             self.adhesion = (float(adhesion[0]), float(adhesion[1]))
             self.stance = self.stance_bins(sim.model, fly, *([float(adhesion[2])] if len(adhesion) == 3 else []))
-        self.act_ids = sim.replay_ids(fly_name, with_adhesion=adhesion is not None)
-        if len(self.leg_columns) != self.n_given:        # position actuators off the legs: their ctrl columns are not the table's
-            keep = [*self.leg_columns.tolist(), *range(self.n_given, int(self.act_ids.numel()))]
-            self.act_ids = self.act_ids[sim._torch.as_tensor(keep, device=sim.device)].contiguous()
+        self.act_ids, self.n_act = _table_columns(self, sim, fly_name, adhesion is not None)
         n_pos = len(self.actuated_dofs)
-        self.n_act = n_pos + (6 if adhesion is not None else 0)
-        if int(self.act_ids.numel()) != self.n_act:
-            raise ValueError(f"the fly has {int(self.act_ids.numel())} actuators for a table of {self.n_act} columns")
         check_params(_CpgParams, "nmf_cpg_params_size", "controllers.py")
         on, off = self.adhesion or (0.0, 0.0)
         self._params = _CpgParams(n_pos, self.n_bins, self.frequency, self.timestep, self.coupling, self.convergence, on, off,
@@ -415,6 +427,183 @@ class HybridTurningCPG(TurningCPG):
                                                 self.swing.ctypes.data, self.root_seg, self.tip_seg.ctypes.data))
         self.retraction, self.stumbling, self.rule_flags = (_field_view(sim, lib.nmf_cpg_field_ptr, self._h, which, typestr)
                                                             for which, typestr in ((3, "<f4"), (4, "<f4"), (5, "|u1")))
+
+
+RULE_NAMES = ("rule1", "rule2_ipsi", "rule2_contra", "rule3_ipsi", "rule3_contra")
+RULE_WEIGHTS = {"rule1": -10.0, "rule2_ipsi": 2.5, "rule2_contra": 1.0, "rule3_ipsi": 3.0, "rule3_contra": 2.0}
+
+
+def default_rules_graph() -> dict:
+    """``{rule name: [(source leg, target leg), ...]}``: rule 1 from a leg to its posterior neighbour, rule 2 from a leg to its
+    anterior neighbour and both ways across each contralateral pair, rule 3 from a leg to its posterior neighbour and both ways
+    across each contralateral pair."""
+    backwards = [(f"{side}{a}", f"{side}{b}") for side in "lr" for a, b in ("fm", "mh")]
+    across = [(f"{a}{pos}", f"{b}{pos}") for pos in "fmh" for a, b in ("lr", "rl")]
+    return {"rule1": backwards, "rule2_ipsi": [(b, a) for a, b in backwards], "rule2_contra": across, "rule3_ipsi": backwards,
+            "rule3_contra": across}
+
+
+def rule_matrices(rules_graph=None, weights=None) -> np.ndarray:
+    """``(3, 6, 6)`` float32 ``[rule][source][target]``, legs in ``LEGS`` order: the matrices W1, W2, W3 of
+    :class:`RuleBasedController`.  ``rules_graph`` replaces the edge lists of the rule names it holds in
+    :func:`default_rules_graph`, ``weights`` the values it holds in ``RULE_WEIGHTS``; an edge listed under both names of a rule
+    gets the sum.  Needs no GPU."""
+    graph, values = default_rules_graph(), dict(RULE_WEIGHTS)
+    for name, given, known in (("rules_graph", rules_graph, graph), ("weights", weights, values)):
+        for key, value in (given or {}).items():
+            if key not in RULE_NAMES:
+                raise ValueError(f"{name} takes the keys {', '.join(RULE_NAMES)}, got {key!r}")
+            known[key] = value
+    out = np.zeros((3, 6, 6), dtype=np.float32)
+    for key in RULE_NAMES:
+        weight = float(values[key])
+        if not np.isfinite(weight):
+            raise ValueError(f"the weight of {key} is not finite: {values[key]!r}")
+        for edge in graph[key]:
+            if len(edge) != 2 or edge[0] not in LEGS or edge[1] not in LEGS:
+                raise ValueError(f"an edge of {key} is a pair of legs out of {', '.join(LEGS)}, got {edge!r}")
+            out[int(key[4]) - 1, LEGS.index(edge[0]), LEGS.index(edge[1])] += np.float32(weight)
+    return out
+
+
+def swing_runs(stance) -> tuple:
+    """``(start_bin[6], swing_bins[6])`` int32 of a stance table ``(n_bins, 6)``: per leg the first bin and the length of the longest
+    circular run of swing bins (the bins that are not stance); of runs of equal length the one that starts at the lowest bin.  A leg
+    whose bins are all swing or all stance raises ``ValueError``.  Needs no GPU."""
+    swing = ~np.asarray(stance, dtype=bool)
+    if swing.ndim != 2 or swing.shape[1] != 6 or swing.shape[0] < 2:
+        raise ValueError(f"a stance table is (n_bins >= 2, 6), got {swing.shape}")
+    n = swing.shape[0]
+    start, length = np.zeros(6, dtype=np.int32), np.zeros(6, dtype=np.int32)
+    for leg in range(6):
+        col = swing[:, leg]
+        if col.all() or not col.any():
+            raise ValueError(f"leg {LEGS[leg]} is in {'swing' if col.all() else 'stance'} in every bin")
+        for b in range(n):
+            if col[b] and not col[b - 1]:                # a run starts here (bin -1 is the last one)
+                run = 1
+                while col[(b + run) % n]:
+                    run += 1
+                if run > length[leg]:
+                    start[leg], length[leg] = b, run
+    return start, length
+
+
+class _RulesParams(ctypes.Structure):
+    """``nmf_rules_params`` of include/nmf.h."""
+
+    _fields_ = [("n_pos", ctypes.c_int32), ("n_bins", ctypes.c_int32), ("period_steps", ctypes.c_int32), ("table_steps", ctypes.c_int32),
+                ("adhesion", ctypes.c_int32), ("adhesion_on", ctypes.c_float), ("adhesion_off", ctypes.c_float), ("margin", ctypes.c_float),
+                ("max_amplitude", ctypes.c_float), ("seed", ctypes.c_uint32), ("first_world", ctypes.c_int32)]
+
+
+class RuleBasedController(NativeHandle, TripodCPG):
+    """Rule-based walking of one fly of a :class:`~flygym_amd.HIPSimulation`, advanced on the GPU (``nmf_rules_advance``,
+    ``csrc/nmf_rules.hip``): every leg decides by Cruse's rules when to start a step, in the form of flygym 1.x's decentralised
+    rule-based controller.  No gait is programmed; tripod, tetrapod and wave gaits follow from the weights.
+
+    Build-defined and pinned by nothing (the reference ships no controllers; nothing is claimed about matching flygym 1.x): the rule
+    graph and the weights are flygym 1.x's as remembered, the statement of the model is include/nmf.h (``nmf_rules_advance``), its
+    specification in numpy tests/rules_spec.py.  Per leg a counter ``k`` in ``[0, P)``: 0 rests at the pose where the leg's swing
+    starts, and a step runs the leg's cycle of :class:`TripodCPG` once in ``P`` physics steps, swing first.  Per physics step, from
+    the six counters alone (the rules read neither the pose nor the contact sensors)::
+
+        swinging_s = 0 < k_s < swing_steps[s];   p_s = max(0, k_s - swing_steps[s]) / (P - swing_steps[s])     (stance progress)
+        score_t = sum_s swinging_s W1[s][t]  +  sum_{p_s > 0} W2[s][t] (1 - p_s)  +  sum_{p_s > 0} W3[s][t] p_s
+        eligible_t = score_t > 0, within ``margin`` of the best score, not stepping, and drive[side_t] != 0
+        nobody stepping and nobody eligible: every leg of a driven side is eligible       (the walk starts, or starts again)
+        one eligible leg, drawn uniformly, starts a step with the amplitude a = min(|drive[side]|, max_amplitude)
+        target[col] = rest + a (c - rest),  c = the step cycle interpolated at k / P,  rest = the cycle where the swing starts
+
+    The draw is a counter-based hash of ``(seed, first_world + w, ticks[w])``, the plume's with a draw index of its own, so a
+    world's walk does not depend on the batch it is stepped in and a captured tick draws afresh on every replay.
+
+    Args:
+        sim: the batch; for a world with several flies ``sim.for_fly(fly_name)``.
+        fly_name: the fly whose position (and adhesion) actuators the table drives.
+        frequency: steps of a leg per second; period_steps: ``P``, default ``round(1 / (frequency * timestep))``.
+        n_phase_bins: bins of the step cycle.
+        adhesion: ``(on, off)`` or ``(on, off, threshold)`` appends six adhesion columns: ``off`` while the leg swings.
+        table_steps: rows per world of the controller's own table: the most steps of one :meth:`advance`.
+        rules_graph, weights: see :func:`rule_matrices`.
+        margin: a leg is eligible when its score is at least ``best - |best| * margin``.
+        max_amplitude: the cap of a step's amplitude.
+        seed, first_world: the draws; ``first_world`` places a shard of worlds inside a larger population.
+
+    ``counter`` ``(n, 6)`` int32, ``stepping`` ``(n, 6)`` uint8, ``amplitude`` ``(n, 6)`` float32, ``drive`` ``(n, 2)`` float32,
+    ``ticks`` ``(n,)`` (the device's uint32 counter seen as int32) and ``scores`` ``(n, 6)`` float32 (of the last step) are zero-copy
+    views of the device state, writable between launches.  ``drive`` has the shape of ``TurningCPG.drive`` and its meaning of
+    magnitude — ``SensorySteering.update(out=ctl.drive)`` and ``PlumeNavigator.update(..., out=ctl.drive)`` steer it unchanged —
+    but the sign of a drive is ignored: legs only ever step forwards, and a side whose drive is 0 starts no step.  A new
+    controller is reset: every leg at rest, drive ``(1, 1)``.
+    """
+
+    _advance_entry = "nmf_rules_advance"
+    _destroy_entry, _noun = "nmf_rules_destroy", "controller"
+    _views = ("counter", "stepping", "amplitude", "drive", "ticks", "scores")
+
+    def __init__(self, sim, fly_name: str, *, frequency: float = 12.0, period_steps: int | None = None, n_phase_bins: int = 256,
+                 adhesion=None, table_steps: int = 64, rules_graph=None, weights=None, margin: float = 1e-3, max_amplitude: float = 1.5,
+                 seed: int = 0, first_world: int = 0):
+        sim = fly_batch(sim, fly_name, resolve=False)
+        if fly_name not in sim.world.fly_lookup:
+            raise ValueError(f"no fly named {fly_name!r} in this simulation ({', '.join(sim.world.fly_lookup)})")
+        if int(table_steps) < 1:
+            raise ValueError(f"table_steps must be at least 1, got {table_steps}")
+        if int(n_phase_bins) < 2:
+            raise ValueError(f"n_phase_bins must be at least 2, got {n_phase_bins}")
+        if period_steps is None:
+            if not (np.isfinite(frequency) and frequency > 0):
+                raise ValueError(f"frequency must be positive and finite, got {frequency!r}")
+            period_steps = round(1.0 / (float(frequency) * float(sim.timestep)))
+        period = int(period_steps)
+        if period < 2 or period * int(n_phase_bins) >= 2 ** 31:
+            raise ValueError(f"period_steps must be at least 2 with period_steps * n_phase_bins below 2^31, got {period} * {n_phase_bins}")
+        if adhesion is not None and len(adhesion) not in (2, 3):
+            raise ValueError(f"adhesion must be (on, off) or (on, off, threshold), got {adhesion!r}")
+        for name, value in (("margin", margin), ("max_amplitude", max_amplitude)):
+            if not (np.isfinite(value) and value >= 0):
+                raise ValueError(f"{name} must be finite and not negative, got {value!r}")
+        if int(first_world) < 0:
+            raise ValueError(f"first_world must not be negative, got {first_world}")
+        self.weights = rule_matrices(rules_graph, weights)
+        fly = sim.world.fly_lookup[fly_name]
+        super().__init__(fly.get_actuated_jointdofs_order("position"), sim.timestep, frequency=frequency, n_phase_bins=n_phase_bins)
+        self.sim, self.fly_name = sim, fly_name
+        self.n_worlds, self.table_steps, self.period_steps = int(sim.n_worlds), int(table_steps), period
+        self.margin, self.max_amplitude = float(margin), float(max_amplitude)
+        self.seed, self.first_world = int(seed) & 0xFFFFFFFF, int(first_world)
+        self.adhesion = None if adhesion is None else (float(adhesion[0]), float(adhesion[1]))
+        self.stance = self.stance_bins(sim.model, fly, *([float(adhesion[2])] if adhesion is not None and len(adhesion) == 3 else []))
+        self.start_bin, self.swing_bins = swing_runs(self.stance)
+        self.swing_steps = ((self.swing_bins.astype(np.int64) * period + self.n_bins - 1) // self.n_bins).astype(np.int32)
+        if (self.swing_steps >= period).any():
+            raise ValueError(f"a swing of {self.swing_steps.tolist()} steps leaves no stance in a period of {period} steps")
+        self.act_ids, self.n_act = _table_columns(self, sim, fly_name, adhesion is not None)
+        check_params(_RulesParams, "nmf_rules_params_size", "controllers.py")
+        on, off = self.adhesion or (0.0, 0.0)
+        self._params = _RulesParams(len(self.actuated_dofs), self.n_bins, period, self.table_steps, int(adhesion is not None), on, off,
+                                    self.margin, self.max_amplitude, self.seed, self.first_world)
+        cycle = np.ascontiguousarray(self.cycle, dtype=np.float32)
+        legs = np.ascontiguousarray(self.leg_of_dof, dtype=np.int32)
+        h = self._create("nmf_rules_create", sim._batch_h, ctypes.byref(self._params), cycle.ctypes.data, legs.ctypes.data,
+                         self.start_bin.ctypes.data, self.swing_steps.ctypes.data, self.weights.ctypes.data)
+        view = lambda which, typestr: _field_view(sim, _native.lib().nmf_rules_field_ptr, h, which, typestr)
+        self.counter, self.stepping, self.amplitude = view(0, "<i4"), view(1, "|u1"), view(2, "<f4")
+        self.drive, self.ticks, self.scores = view(3, "<f4"), view(4, "<i4").reshape(self.n_worlds), view(5, "<f4")
+        t = sim._torch
+        self.table = t.zeros((self.n_worlds, self.table_steps, self.n_act), dtype=t.float32, device=sim.device)
+
+    # the drive, the launch and the control tick are TurningCPG's, word for word: both write the table nmf_step_replay reads
+    set_drive, advance, step = TurningCPG.set_drive, TurningCPG.advance, TurningCPG.step
+
+    def reset(self, mask=None) -> None:
+        """The worlds of ``mask`` (``(n_worlds,)`` bool, numpy or torch; default all) start again: every leg at rest, amplitude 1,
+        ``drive = (1, 1)``, tick 0 (their draws from the start), scores 0; the others keep their state.  Stream-ordered device work
+        (no host sync)."""
+        h = self._handle()
+        m = reset_mask(mask, self.n_worlds, self.sim)
+        _native.check(_native.lib().nmf_rules_reset(h, None if m is None else m.data_ptr(), self.sim._stream()))
 
 
 class _TaxisParams(ctypes.Structure):

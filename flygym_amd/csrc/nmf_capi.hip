@@ -20,9 +20,9 @@
 #include "nmf_step.hip"
 #include "nmf_sensors.hip"
 // `#pragma clang fp reassociate(off)` at file scope holds from the first file that sets it to the end of the translation unit:
-// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip, nmf_plume.hip, nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip, nmf_navigator.hip, nmf_stabilizer.hip and the host code
+// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip, nmf_plume.hip, nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip, nmf_navigator.hip, nmf_stabilizer.hip, nmf_rules.hip and the host code
 // below are all compiled under it, and the files above are not.  Which files it covers decides their kernels' arithmetic: keep the
-// order (nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip, nmf_navigator.hip and nmf_stabilizer.hip add pragmas inside their functions only: nothing of them reaches past the file).
+// order (nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip, nmf_navigator.hip, nmf_stabilizer.hip and nmf_rules.hip add pragmas inside their functions only: nothing of them reaches past the file).
 #include "nmf_eyes.hip"
 #include "nmf_camera.hip"
 #include "nmf_replay.hip"
@@ -33,6 +33,7 @@
 #include "nmf_motion.hip"
 #include "nmf_navigator.hip"
 #include "nmf_stabilizer.hip"
+#include "nmf_rules.hip"
 #include "nmf_skeleton.h"      // nmf_model, the blob parser, classify_skeleton
 #endif
 
@@ -65,7 +66,7 @@ struct DeviceGuard {
   DeviceGuard guard_((b)->mem.device);                                                        \
   if (guard_.err != hipSuccess) return fail(std::string("hipSetDevice: ") + hipGetErrorString(guard_.err))
 
-// The device memory of one handle (batch, eye plan, camera plan, CPG, plume, odometry, motion, navigator, stabilizer): every allocation is 16-byte granular, recorded, and freed
+// The device memory of one handle (batch, eye plan, camera plan, CPG, plume, odometry, motion, navigator, stabilizer, rules): every allocation is 16-byte granular, recorded, and freed
 // with the handle.  The first failure sets the error text, named after the entry point `who`, and sticks: later calls return
 // null without touching the device, so that a caller tests `ok` once after its last allocation.
 struct DevMem {
@@ -1304,21 +1305,28 @@ extern "C" void* nmf_cpg_field_ptr(nmf_cpg* C, int which, int32_t* width) {
   return ptr[which];
 }
 
-// Pure stream-ordered work: argument checks on the host, one kernel launch (with the hybrid rules or without).
-static int cpg_advance(const char* who, bool hybrid, nmf_cpg* C, int n_steps, float* table_dev, int table_steps, void* stream) {
-  const std::string w(who);
-  if (!C) return fail(w + ": null controller");
+// What every advance of a controller (nmf_cpg_advance, nmf_cpg_advance_hybrid, nmf_rules_advance) checks of its table before it
+// launches; `made_for`: the controller's table_steps, `device`: its device, which the caller has made current.
+static int check_table(const std::string& w, int made_for, int device, int n_steps, float* table_dev, int table_steps, void* stream) {
   if (!table_dev) return fail(w + ": null table");
-  if (table_steps != C->table_steps) return fail(w + ": the controller was made for tables of " + std::to_string(C->table_steps) + " steps, got " + std::to_string(table_steps));
+  if (table_steps != made_for) return fail(w + ": the controller was made for tables of " + std::to_string(made_for) + " steps, got " + std::to_string(table_steps));
   if (n_steps < 1 || n_steps > table_steps) return fail(w + ": n_steps must be in 1.." + std::to_string(table_steps) + ", got " + std::to_string(n_steps));
-  DEVICE_GUARD(C);
   // the table must live on the controller's device (a pointer query is no stream work, but a capture is left alone)
   hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing((hipStream_t)stream, &capturing) == hipSuccess && capturing == hipStreamCaptureStatusNone) {
     hipPointerAttribute_t at{};
     if (hipPointerGetAttributes(&at, table_dev) != hipSuccess) { (void)hipGetLastError(); return fail(w + ": the table is not device memory"); }
-    if (at.device != C->mem.device) return fail(w + ": the controller was made for device " + std::to_string(C->mem.device) + ", the table is on device " + std::to_string(at.device));
+    if (at.device != device) return fail(w + ": the controller was made for device " + std::to_string(device) + ", the table is on device " + std::to_string(at.device));
   }
+  return 0;
+}
+
+// Pure stream-ordered work: argument checks on the host, one kernel launch (with the hybrid rules or without).
+static int cpg_advance(const char* who, bool hybrid, nmf_cpg* C, int n_steps, float* table_dev, int table_steps, void* stream) {
+  const std::string w(who);
+  if (!C) return fail(w + ": null controller");
+  DEVICE_GUARD(C);
+  if (check_table(w, C->table_steps, C->mem.device, n_steps, table_dev, table_steps, stream) != 0) return -1;
   if (hybrid && !C->hybrid) return fail(w + ": the hybrid rules are not enabled (nmf_cpg_hybrid_enable)");
   const dim3 grid((unsigned)((C->n_worlds + nmf::kCpgWorlds - 1) / nmf::kCpgWorlds)), block(nmf::kCpgThreads);
   if (hybrid)
@@ -1966,6 +1974,116 @@ extern "C" int nmf_stabilizer_update(nmf_stabilizer* S, float* out_dev, void* st
   hipLaunchKernelGGL(nmf::nmf_stabilizer_update_kernel, dim3((unsigned)((S->n_worlds + nmf::kStabLanes - 1) / nmf::kStabLanes)), dim3(nmf::kStabLanes * nmf::kStabWaves),
                      S->lds_bytes, (hipStream_t)stream, S->args, S->qpos, S->sensordata, S->dof, S->mean, S->inv_std, S->blob, S->ctrl,
                      out_dev ? out_dev : S->out);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// ---- rule-based walking (nmf_rules.hip) ----
+// The controller's shared tables (own device copies) and its per-world state.
+struct nmf_rules {
+  int n_worlds = 0, table_steps = 0;
+  nmf::RulesArgs args{};
+  nmf::RulesPtrs ptrs{};
+  DevMem mem;
+};
+
+extern "C" size_t nmf_rules_params_size(void) { return sizeof(nmf_rules_params); }
+
+extern "C" void nmf_rules_destroy(nmf_rules* R) {
+  if (!R) return;
+  R->mem.release();
+  delete R;
+}
+
+extern "C" int nmf_rules_reset(nmf_rules* R, const uint8_t* mask_dev, void* stream) {
+  if (!R) return fail("nmf_rules_reset: null controller");
+  DEVICE_GUARD(R);
+  hipLaunchKernelGGL(nmf::nmf_rules_reset_kernel, dim3((unsigned)((6 * R->n_worlds + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     R->n_worlds, mask_dev, R->ptrs);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+static int fill_rules(nmf_rules* R, const nmf_rules_params* p, const float* cycle, const int32_t* leg_of_col, const int32_t* start_bin,
+                      const int32_t* swing_steps, const float* weights) {
+  const std::string who = "nmf_rules_create: ";
+  if (p->n_pos < 1 || p->n_pos > 4096) return fail(who + "need 1 <= n_pos <= 4096 position columns");
+  if (p->n_bins < 2 || p->n_bins > (1 << 20)) return fail(who + "need 2 <= n_bins <= 2^20 phase bins");
+  if (p->table_steps < 1) return fail(who + "table_steps must be at least 1");
+  if (p->period_steps < 2) return fail(who + "period_steps must be at least 2, got " + std::to_string(p->period_steps));
+  if ((int64_t)p->period_steps * (int64_t)p->n_bins >= (int64_t)1 << 31)
+    return fail(who + "period_steps * n_bins must be below 2^31, got " + std::to_string(p->period_steps) + " * " + std::to_string(p->n_bins));
+  for (int c = 0; c < p->n_pos; ++c)
+    if (leg_of_col[c] < 0 || leg_of_col[c] > 5) return fail(who + "leg_of_col[" + std::to_string(c) + "] is outside 0..5");
+  for (int l = 0; l < 6; ++l) {
+    if (start_bin[l] < 0 || start_bin[l] >= p->n_bins) return fail(who + "start_bin[" + std::to_string(l) + "] is outside 0 .. n_bins - 1");
+    if (swing_steps[l] < 1 || swing_steps[l] >= p->period_steps)
+      return fail(who + "swing_steps[" + std::to_string(l) + "] = " + std::to_string(swing_steps[l]) + " is outside 1 .. period_steps - 1");
+  }
+  for (int i = 0; i < 108; ++i)
+    if (!std::isfinite(weights[i])) return fail(who + "a weight is not finite");
+  const float values[4] = {p->margin, p->max_amplitude, p->adhesion_on, p->adhesion_off};
+  for (float v : values)
+    if (!std::isfinite(v)) return fail(who + "margin, max_amplitude or an adhesion value is not finite");
+  if (p->margin < 0.f || p->max_amplitude < 0.f) return fail(who + "margin and max_amplitude must not be negative");
+  if (p->first_world < 0) return fail(who + "first_world must not be negative");
+  nmf::RulesArgs& A = R->args;
+  A.n_worlds = R->n_worlds; A.n_pos = p->n_pos; A.n_act = p->n_pos + (p->adhesion ? 6 : 0); A.n_bins = p->n_bins; A.period = p->period_steps;
+  A.margin = p->margin; A.max_amplitude = p->max_amplitude; A.adhesion_on = p->adhesion_on; A.adhesion_off = p->adhesion_off;
+  A.seed = p->seed; A.first_world = p->first_world;
+  R->table_steps = p->table_steps;
+  std::vector<float> rest((size_t)p->n_pos);
+  for (int c = 0; c < p->n_pos; ++c) rest[(size_t)c] = cycle[(size_t)start_bin[leg_of_col[c]] * p->n_pos + c];
+  const size_t n = (size_t)R->n_worlds;
+  nmf::RulesPtrs& P = R->ptrs;
+  P.cycle = (const float*)R->mem.upload(cycle, sizeof(float) * (size_t)p->n_bins * (size_t)p->n_pos);
+  P.rest = (const float*)R->mem.upload(rest.data(), sizeof(float) * rest.size());
+  P.leg_of_col = (const int*)R->mem.upload(leg_of_col, sizeof(int) * (size_t)p->n_pos);
+  P.start_bin = (const int*)R->mem.upload(start_bin, sizeof(int) * 6);
+  P.swing_steps = (const int*)R->mem.upload(swing_steps, sizeof(int) * 6);
+  P.weights = (const float*)R->mem.upload(weights, sizeof(float) * 108);
+  P.counter = (int*)R->mem.alloc(sizeof(int) * 6 * n);
+  P.stepping = (uint8_t*)R->mem.alloc(6 * n);
+  P.amplitude = (float*)R->mem.alloc(sizeof(float) * 6 * n);
+  P.drive = (float*)R->mem.alloc(sizeof(float) * 2 * n);
+  P.ticks = (unsigned int*)R->mem.alloc(sizeof(unsigned int) * n);
+  P.scores = (float*)R->mem.alloc(sizeof(float) * 6 * n);
+  if (!R->mem.ok) return -1;
+  if (nmf_rules_reset(R, nullptr, nullptr) != 0) return -1;
+  HIP_OK(hipDeviceSynchronize());
+  return 0;
+}
+
+extern "C" nmf_rules* nmf_rules_create(nmf_batch* b, const nmf_rules_params* p, const float* cycle, const int32_t* leg_of_col,
+                                       const int32_t* start_bin, const int32_t* swing_steps, const float* weights) {
+  if (!b || !p) { fail("nmf_rules_create: null batch / params"); return nullptr; }
+  if (!cycle || !leg_of_col || !start_bin || !swing_steps || !weights) {
+    fail("nmf_rules_create: cycle, leg_of_col, start_bin, swing_steps and weights are required"); return nullptr;
+  }
+  return build_or_destroy(b->mem.device, "nmf_rules_create", new nmf_rules(), nmf_rules_destroy, [&](nmf_rules* R) {
+    R->n_worlds = b->n_worlds;
+    return fill_rules(R, p, cycle, leg_of_col, start_bin, swing_steps, weights);
+  });
+}
+
+extern "C" void* nmf_rules_field_ptr(nmf_rules* R, int which, int32_t* width) {
+  if (!R) { fail("nmf_rules_field_ptr: null controller"); return nullptr; }
+  const nmf::RulesPtrs& P = R->ptrs;
+  void* ptr[6] = {P.counter, P.stepping, P.amplitude, P.drive, P.ticks, P.scores};
+  const int32_t w[6] = {6, 6, 6, 2, 1, 6};
+  if (which < 0 || which > 5) { fail("nmf_rules_field_ptr: no such field"); return nullptr; }
+  if (width) *width = w[which];
+  return ptr[which];
+}
+
+// Pure stream-ordered work: argument checks on the host, one kernel launch.
+extern "C" int nmf_rules_advance(nmf_rules* R, int n_steps, float* table_dev, int table_steps, void* stream) {
+  const std::string w = "nmf_rules_advance";
+  if (!R) return fail(w + ": null controller");
+  DEVICE_GUARD(R);
+  if (check_table(w, R->table_steps, R->mem.device, n_steps, table_dev, table_steps, stream) != 0) return -1;
+  hipLaunchKernelGGL(nmf::nmf_rules_advance_kernel, dim3((unsigned)((R->n_worlds + nmf::kRulesWorlds - 1) / nmf::kRulesWorlds)), dim3(nmf::kRulesThreads),
+                     0, (hipStream_t)stream, R->args, R->ptrs, table_dev, table_steps, n_steps);
   HIP_OK(hipGetLastError());
   return 0;
 }

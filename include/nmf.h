@@ -32,6 +32,7 @@ typedef struct nmf_odometry nmf_odometry;
 typedef struct nmf_motion nmf_motion;
 typedef struct nmf_navigator nmf_navigator;
 typedef struct nmf_stabilizer nmf_stabilizer;
+typedef struct nmf_rules nmf_rules;
 
 /* Per-world fields addressable through nmf_field_ptr / nmf_gather_* */
 enum nmf_field {
@@ -888,6 +889,91 @@ int nmf_stabilizer_update(nmf_stabilizer* stabilizer, float* out_dev, void* stre
 /* Device pointer + row width of an array of the handle (zero-copy view; writable between launches). */
 #define NMF_STABILIZER_OUTPUT 0     /* [n_out] float32: the output array of the handle's own (starts at 0)     */
 void* nmf_stabilizer_field_ptr(nmf_stabilizer* stabilizer, int which, int32_t* width);
+
+/* Rule-based walking with its state on the device (flygym_amd.controllers.RuleBasedController; csrc/nmf_rules.hip): legs start
+ * steps by Cruse's rules 1 to 3, in the form of flygym 1.x's decentralised rule-based controller.  No reference counterpart (the
+ * snapshot holds no controllers): build-defined and pinned by nothing (specification tests/rules_spec.py).
+ * Tripod, tetrapod and wave gaits are not programmed: they follow from the weights.
+ * Legs in LEGS order lf lm lh rf rm rh, side = leg / 3.  State per (world, leg): the counter k (int32, 0 <= k < P: 0 rests, a step
+ * runs the leg's cycle once in P physics steps, swing first), stepping (uint8) and the latched amplitude a (float32).  State per
+ * world: drive[2] (float32: left, right, the order of NMF_CPG_DRIVE) and the tick word (uint32, physics steps since the reset: the
+ * noise counter).  Shared: P = period_steps; cycle[n_bins][n_pos] and leg_of_col[n_pos] as nmf_cpg_create takes them; per leg
+ * start_bin[l], the bin its swing starts at, and swing_steps[l], the physics steps its swing lasts (1 .. P - 1); three weight
+ * matrices W1, W2, W3 [src][tgt]; margin; max_amplitude.
+ * One physics step of one world.  The drive is read once when the launch starts.  All float arithmetic is float32, every operation
+ * rounded once as written (no contraction, no reassociation), clamps are comparisons.
+ *   1. the row, from the state before the update, for leg l:
+ *        x = (double)(k n_bins) / (double)P  (one correctly rounded float64 division),  i0 = floor(x),  f = (float)(x - i0)
+ *        b0 = (start_bin[l] + i0) mod n_bins,  b1 = (b0 + 1) mod n_bins
+ *        c = fl(fl(1 - f) cycle[b0][col]) + fl(f cycle[b1][col]),  rest = cycle[start_bin[l]][col]
+ *        row[col] = rest + fl(a fl(c - rest))                         (a resting leg holds rest exactly, whatever a is)
+ *        row[n_pos + l] = adhesion_off while 0 < k < swing_steps[l], else adhesion_on      (with the six adhesion columns)
+ *   2. the scores, a pure function of the six counters:
+ *        swinging_s = 0 < k_s < swing_steps[s]
+ *        p_s = (float)max(0, k_s - swing_steps[s]) / (float)(P - swing_steps[s])           (correctly rounded)
+ *        for target t, sources s ascending, each sum from 0:  r1 = sum (swinging_s ? W1[s][t] : 0)
+ *        r2 = sum over p_s > 0 of fl(W2[s][t] fl(1 - p_s)),  r3 = sum over p_s > 0 of fl(W3[s][t] p_s),  score_t = (r1 + r2) + r3
+ *   3. eligibility:  m = max_t score_t;  x = m - fl(|m| margin);  thr = x > 0 ? x : 0
+ *        eligible_t = score_t >= thr and score_t > 0 and not stepping_t and drive[side_t] != 0
+ *        the fallback: if no leg of the world is stepping and none is eligible, every leg with drive[side_t] != 0 is eligible
+ *        (this starts the walk after a reset and starts it again after a stop)
+ *   4. selection, n = the number of eligible legs, if n > 0:
+ *        u = hash(seed ^ (first_world + w) 0x9E3779B9 ^ tick 0x85EBCA6B ^ NMF_RULES_DRAW 0xC2B2AE35)      (uint32 arithmetic: the
+ *        mixer and the key of csrc/nmf_plume.hip, whose wind noise uses the draw indices 0..7 and the navigator 8..10)
+ *        j = ((uint64)u n) >> 32;  the j-th eligible leg in ascending order gets stepping = 1 and
+ *        a = |drive[side]| > max_amplitude ? max_amplitude : |drive[side]|               (the sign of a drive is ignored)
+ *   5. advance: stepping legs k <- k + 1; at k = P: k <- 0, stepping <- 0
+ *   6. tick <- tick + 1
+ * scores keeps score_t of the last step.  A world's result depends on (seed, first_world + w, its state and its drive) alone: not on
+ * the batch it is stepped in. */
+#define NMF_RULES_DRAW 11            /* the draw index of the selection */
+typedef struct nmf_rules_params {
+  int32_t n_pos;                /* position-target columns of a row (1..4096)                                            */
+  int32_t n_bins;               /* phase bins of the step cycle (2..2^20)                                                */
+  int32_t period_steps;         /* P: physics steps of one step of a leg (>= 2, P n_bins < 2^31)                         */
+  int32_t table_steps;          /* rows per world of the tables nmf_rules_advance will be given (>= 1)                   */
+  int32_t adhesion;             /* != 0: six adhesion columns follow the position columns                                */
+  float adhesion_on, adhesion_off;   /* their values out of swing / in swing                                            */
+  float margin;                 /* relative distance from the best score within which a leg is eligible (>= 0)           */
+  float max_amplitude;          /* the cap of the latched amplitude (>= 0)                                               */
+  uint32_t seed;                /* of the selection's draws                                                              */
+  int32_t first_world;          /* global index of world 0 (a shard of a larger population); >= 0                        */
+} nmf_rules_params;
+
+/* sizeof(nmf_rules_params) as this library was compiled (as nmf_eye_params_size). */
+size_t nmf_rules_params_size(void);
+
+/* An explicit handle for the worlds of `batch`, on its device: takes HOST arrays — cycle[n_bins][n_pos] float32, leg_of_col[n_pos]
+ * (each in 0..5), start_bin[6] (each in 0 .. n_bins - 1), swing_steps[6] (each in 1 .. P - 1), weights[3][6][6] float32 (W1, W2, W3
+ * as [src][tgt]) — validates them, owns device copies and the state arrays, and resets every world (nmf_rules_reset with a NULL
+ * mask).  NOT stream-ordered (allocations, synchronous uploads); must not be called inside a stream capture.  NULL on error
+ * (nmf_last_error), with nothing left allocated: a size outside the ranges above; P n_bins >= 2^31; a leg_of_col, start_bin or
+ * swing_steps outside its range; a weight, margin, max_amplitude or adhesion value that is not finite; a negative margin,
+ * max_amplitude or first_world; a null argument; no device memory. */
+nmf_rules* nmf_rules_create(nmf_batch* batch, const nmf_rules_params* params, const float* cycle, const int32_t* leg_of_col,
+                            const int32_t* start_bin, const int32_t* swing_steps, const float* weights);
+void nmf_rules_destroy(nmf_rules* rules);
+
+/* The worlds with mask_dev[w] != 0 (uint8 per world, device memory; NULL: all) get k = 0, stepping = 0, a = 1, drive = (1, 1),
+ * tick = 0 (their draws start again) and scores = 0; the others are not touched.  Stream-ordered. */
+int nmf_rules_reset(nmf_rules* rules, const uint8_t* mask_dev, void* stream);
+
+/* Device pointer + row width of a per-world array of the controller (zero-copy views; writable between launches).  A counter
+ * written outside [0, P) is reduced modulo P by the next launch. */
+#define NMF_RULES_COUNTER 0       /* [6] int32                     */
+#define NMF_RULES_STEPPING 1      /* [6] uint8                     */
+#define NMF_RULES_AMPLITUDE 2     /* [6] float32                   */
+#define NMF_RULES_DRIVE 3         /* [2] float32 (left, right)     */
+#define NMF_RULES_TICKS 4         /* [1] uint32                    */
+#define NMF_RULES_SCORES 5        /* [6] float32                   */
+void* nmf_rules_field_ptr(nmf_rules* rules, int which, int32_t* width);
+
+/* Advance every world by n_steps and write table_dev[w][s][0 .. n_act) for s < n_steps (float32 [n_worlds][table_steps][n_act],
+ * n_act = n_pos or n_pos + 6: the table of nmf_step_replay / nmf_step_record with start = 0); rows n_steps .. table_steps - 1 are
+ * not touched.  Argument checks and ONE kernel launch on `stream`: no allocation, no host synchronisation, hipGraph-capturable
+ * (the counters and the tick words live on the device, so a captured launch continues and draws afresh on every replay).
+ * Refused: what nmf_cpg_advance refuses. */
+int nmf_rules_advance(nmf_rules* rules, int n_steps, float* table_dev, int table_steps, void* stream);
 
 /* Odor intensity at n_sensors points rigidly attached to named segments (sensor_seg = index into the
  * batch's segment order, sensor_rel = offset in the segment frame): out[w][d][k] = sum_s peak[s][d] / dist^2.
