@@ -196,6 +196,12 @@ def lib():
             "nmf_motion_reset": (ci, [vp, vp, vp]),
             "nmf_motion_update": (ci, [vp, vp, vp, vp, vp]),
             "nmf_motion_field_ptr": (vp, [vp, ci, ctypes.POINTER(ctypes.c_int32)]),
+            "nmf_visnet_params_size": (ctypes.c_size_t, []),
+            "nmf_visnet_create": (vp, [vp, vp, vp, vp, vp, vp, vp]),
+            "nmf_visnet_destroy": (None, [vp]),
+            "nmf_visnet_reset": (ci, [vp, vp, vp]),
+            "nmf_visnet_update": (ci, [vp, vp, vp, vp, vp]),
+            "nmf_visnet_field_ptr": (vp, [vp, ci, ctypes.POINTER(ctypes.c_int32)]),
             "nmf_navigator_params_size": (ctypes.c_size_t, []),
             "nmf_navigator_create": (vp, [vp, vp]),
             "nmf_navigator_destroy": (None, [vp]),

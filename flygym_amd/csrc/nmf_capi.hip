@@ -20,9 +20,9 @@
 #include "nmf_step.hip"
 #include "nmf_sensors.hip"
 // `#pragma clang fp reassociate(off)` at file scope holds from the first file that sets it to the end of the translation unit:
-// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip, nmf_plume.hip, nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip, nmf_navigator.hip, nmf_stabilizer.hip, nmf_rules.hip and the host code
+// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip, nmf_plume.hip, nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip, nmf_navigator.hip, nmf_stabilizer.hip, nmf_rules.hip, nmf_visnet.hip and the host code
 // below are all compiled under it, and the files above are not.  Which files it covers decides their kernels' arithmetic: keep the
-// order (nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip, nmf_navigator.hip, nmf_stabilizer.hip and nmf_rules.hip add pragmas inside their functions only: nothing of them reaches past the file).
+// order (nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip, nmf_navigator.hip, nmf_stabilizer.hip, nmf_rules.hip and nmf_visnet.hip add pragmas inside their functions only: nothing of them reaches past the file).
 #include "nmf_eyes.hip"
 #include "nmf_camera.hip"
 #include "nmf_replay.hip"
@@ -34,6 +34,7 @@
 #include "nmf_navigator.hip"
 #include "nmf_stabilizer.hip"
 #include "nmf_rules.hip"
+#include "nmf_visnet.hip"
 #include "nmf_skeleton.h"      // nmf_model, the blob parser, classify_skeleton
 #endif
 
@@ -66,7 +67,7 @@ struct DeviceGuard {
   DeviceGuard guard_((b)->mem.device);                                                        \
   if (guard_.err != hipSuccess) return fail(std::string("hipSetDevice: ") + hipGetErrorString(guard_.err))
 
-// The device memory of one handle (batch, eye plan, camera plan, CPG, plume, odometry, motion, navigator, stabilizer, rules): every allocation is 16-byte granular, recorded, and freed
+// The device memory of one handle (batch, eye plan, camera plan, CPG, plume, odometry, motion, navigator, stabilizer, rules, visual network): every allocation is 16-byte granular, recorded, and freed
 // with the handle.  The first failure sets the error text, named after the entry point `who`, and sticks: later calls return
 // null without touching the device, so that a caller tests `ok` once after its last allocation.
 struct DevMem {
@@ -1748,6 +1749,162 @@ extern "C" int nmf_motion_update(nmf_motion* M, const float* omm_dev, const floa
   DEVICE_GUARD(M);
   hipLaunchKernelGGL(nmf::nmf_motion_kernel, dim3((unsigned)((M->n_worlds + nmf::kMotionWorlds - 1) / nmf::kMotionWorlds)), dim3(nmf::kMotionThreads),
                      0, (hipStream_t)stream, M->args, M->ptrs, reinterpret_cast<const float2*>(omm_dev), base_dev, drive_out_dev);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// ---- retinotopic visual network (nmf_visnet.hip) ----
+// The shared network (tap list grouped by post type, neighbour table), the per-world state and the outputs.
+struct nmf_visnet {
+  int n_worlds = 0;
+  nmf::VisArgs args{};
+  nmf::VisPtrs ptrs{};
+  const int4* taps = nullptr;                  // grouped by post type
+  const unsigned int* tables = nullptr;        // per eye, uint16 pairs
+  float* drive = nullptr;
+  unsigned threads = 0, lds_bytes = 0;
+  DevMem mem;
+};
+
+extern "C" size_t nmf_visnet_params_size(void) { return sizeof(nmf_visnet_params); }
+
+extern "C" void nmf_visnet_destroy(nmf_visnet* V) {
+  if (!V) return;
+  V->mem.release();
+  delete V;
+}
+
+extern "C" int nmf_visnet_reset(nmf_visnet* V, const uint8_t* mask_dev, void* stream) {
+  if (!V) return fail("nmf_visnet_reset: null handle");
+  DEVICE_GUARD(V);
+  hipLaunchKernelGGL(nmf::nmf_visnet_reset_kernel, dim3((unsigned)((V->n_worlds + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     V->n_worlds, mask_dev, V->ptrs.fresh);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+static int fill_visnet(nmf_visnet* V, const nmf_visnet_params* p, const float* types, const int32_t* neighbours, const int32_t* edges,
+                       const int32_t* taps, const float* tap_w) {
+  const std::string who = "nmf_visnet_create: ";
+  const int C = p->n_types, n_omm = p->n_omm, T = p->n_table, E = p->n_edges, K = p->n_taps;
+  if (C < 1 || C > NMF_VISNET_MAX_TYPES) return fail(who + "n_types must be in 1..32, got " + std::to_string(C));
+  if (n_omm < 1 || n_omm > nmf::kMaxOmmatidia) return fail(who + "n_omm must be in 1..1024, got " + std::to_string(n_omm));
+  if (C * n_omm > NMF_VISNET_MAX_CELLS)
+    return fail(who + "n_types x n_omm must be at most 24576 cells, got " + std::to_string(C) + " x " + std::to_string(n_omm) + " = " + std::to_string(C * n_omm));
+  if (T < 1 || T > NMF_VISNET_MAX_TABLE) return fail(who + "n_table must be in 1..19, got " + std::to_string(T));
+  if (E < 0 || E > NMF_VISNET_MAX_EDGES) return fail(who + "n_edges must be in 0..512, got " + std::to_string(E));
+  if (K < 0 || K > NMF_VISNET_MAX_TAPS) return fail(who + "n_taps must be in 0..4096, got " + std::to_string(K));
+  if (p->substeps < 1 || p->substeps > NMF_VISNET_MAX_SUBSTEPS) return fail(who + "substeps must be in 1..8, got " + std::to_string(p->substeps));
+  if ((E > 0 && !edges) || (K > 0 && (!taps || !tap_w))) return fail(who + "null edges / taps / tap weights");
+  const float values[5] = {p->gain, p->delta, p->base, p->drive_min, p->drive_max};
+  for (float v : values)
+    if (!std::isfinite(v)) return fail(who + "a parameter is not finite");
+  static const char* const kConstant[5] = {"bias", "in_w[0]", "in_w[1]", "a", "steer_w"};
+  for (int c = 0; c < C; ++c) {
+    for (int f = 0; f < 5; ++f)
+      if (!std::isfinite(types[5 * c + f])) return fail(who + kConstant[f] + " of type " + std::to_string(c) + " is not finite");
+    if (!(types[5 * c + 3] > 0.f) || types[5 * c + 3] > 1.f) return fail(who + "a of type " + std::to_string(c) + " must be in (0, 1]");
+  }
+  // the neighbour table as uint16, a missing neighbour = n_omm (the +0 cell of every LDS row), padded to whole 32-bit words
+  const size_t per_eye = ((size_t)T * (size_t)n_omm + 1) & ~(size_t)1;
+  std::vector<uint16_t> table(2 * per_eye, (uint16_t)n_omm);
+  for (int e = 0; e < 2; ++e)
+    for (int t = 0; t < T; ++t)
+      for (int i = 0; i < n_omm; ++i) {
+        const int32_t j = neighbours[((size_t)e * T + t) * n_omm + i];
+        if (j < -1 || j >= n_omm)
+          return fail(who + "neighbours[" + std::to_string(e) + "][" + std::to_string(t) + "][" + std::to_string(i) + "] = " + std::to_string(j) + " is outside -1.." + std::to_string(n_omm - 1));
+        table[(size_t)e * per_eye + (size_t)t * n_omm + i] = (uint16_t)(j < 0 ? n_omm : j);
+      }
+  for (int e = 0; e < E; ++e)
+    for (int f = 0; f < 2; ++f)
+      if (edges[2 * e + f] < 0 || edges[2 * e + f] >= C)
+        return fail(who + "edge " + std::to_string(e) + " = (" + std::to_string(edges[2 * e]) + ", " + std::to_string(edges[2 * e + 1]) + ") is outside the network's " + std::to_string(C) + " types");
+  for (int k = 0; k < K; ++k) {
+    if (taps[2 * k] < 0 || taps[2 * k] >= E) return fail(who + "tap " + std::to_string(k) + " belongs to edge " + std::to_string(taps[2 * k]) + ", outside the network's " + std::to_string(E) + " edges");
+    if (taps[2 * k + 1] < 0 || taps[2 * k + 1] >= T) return fail(who + "tap " + std::to_string(k) + " reads row " + std::to_string(taps[2 * k + 1]) + ", outside the table's " + std::to_string(T) + " rows");
+    if (!std::isfinite(tap_w[k])) return fail(who + "the weight of tap " + std::to_string(k) + " is not finite");
+  }
+  nmf::VisArgs& A = V->args;
+  A.p = *p;
+  A.n_worlds = V->n_worlds; A.n_omm = n_omm; A.n_types = C; A.n_table = T; A.substeps = p->substeps;
+  A.row = n_omm + 1; A.nb_word = C * A.row; A.nb_words = (int)(per_eye / 2); A.part_word = A.nb_word + A.nb_words;
+  A.den = 65536.0 * (double)n_omm;
+  // the taps grouped by post type: the edges into a type in the caller's order, the taps of an edge in the caller's order
+  std::vector<int32_t> flat((size_t)4 * (size_t)std::max(K, 1), 0);
+  int count = 0;
+  for (int c = 0; c < NMF_VISNET_MAX_TYPES; ++c) {
+    A.start[c] = count;
+    const bool used = c < C;
+    A.bias[c] = used ? types[5 * c] : 0.f; A.in_w0[c] = used ? types[5 * c + 1] : 0.f; A.in_w1[c] = used ? types[5 * c + 2] : 0.f;
+    A.a[c] = used ? types[5 * c + 3] : 0.f; A.steer_w[c] = used ? types[5 * c + 4] : 0.f;
+    for (int e = 0; used && e < E; ++e) {
+      if (edges[2 * e] != c) continue;
+      for (int k = 0; k < K; ++k) {
+        if (taps[2 * k] != e) continue;
+        int32_t* out = &flat[4 * (size_t)count++];
+        out[0] = edges[2 * e + 1] * A.row; out[1] = taps[2 * k + 1] * n_omm;
+        std::memcpy(&out[2], &tap_w[k], sizeof(float));
+      }
+    }
+  }
+  A.start[NMF_VISNET_MAX_TYPES] = count;
+  V->threads = (unsigned)((n_omm + nmf::kWave - 1) / nmf::kWave * nmf::kWave);
+  V->lds_bytes = (unsigned)(sizeof(float) * ((size_t)A.part_word + (size_t)(V->threads / nmf::kWave) * NMF_VISNET_MAX_TYPES));
+  if (V->lds_bytes > 64u * 1024u)
+    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&nmf::nmf_visnet_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)(sizeof(float) * (NMF_VISNET_MAX_CELLS + NMF_VISNET_MAX_TYPES + (NMF_VISNET_MAX_TABLE * nmf::kMaxOmmatidia) / 2 +
+                                                      (nmf::kVisMaxThreads / nmf::kWave) * NMF_VISNET_MAX_TYPES))));
+  const size_t n = (size_t)V->n_worlds;
+  nmf::VisPtrs& P = V->ptrs;
+  V->taps = (const int4*)V->mem.upload(flat.data(), sizeof(int32_t) * flat.size());
+  V->tables = (const unsigned int*)V->mem.upload(table.data(), sizeof(uint16_t) * table.size());
+  P.v = (float*)V->mem.alloc(sizeof(float) * n * 2 * (size_t)C * (size_t)n_omm);
+  P.fresh = (uint8_t*)V->mem.alloc(2 * n);
+  P.sums = (int*)V->mem.alloc(sizeof(int) * n * 2 * (size_t)C);
+  P.pooled = (float*)V->mem.alloc(sizeof(float) * n * 2 * (size_t)C);
+  P.signal = (float*)V->mem.alloc(sizeof(float) * n);
+  const std::vector<float> ones(2 * n, 1.f);
+  V->drive = (float*)V->mem.upload(ones.data(), sizeof(float) * ones.size());
+  if (!V->mem.ok) return -1;
+  if (nmf_visnet_reset(V, nullptr, nullptr) != 0) return -1;
+  HIP_OK(hipDeviceSynchronize());
+  return 0;
+}
+
+extern "C" nmf_visnet* nmf_visnet_create(nmf_batch* b, const nmf_visnet_params* p, const float* types_host, const int32_t* neighbours_host,
+                                         const int32_t* edges_host, const int32_t* taps_host, const float* tap_w_host) {
+  if (!b || !p || !types_host || !neighbours_host) { fail("nmf_visnet_create: null batch / params / types / neighbours"); return nullptr; }
+  return build_or_destroy(b->mem.device, "nmf_visnet_create", new nmf_visnet(), nmf_visnet_destroy, [&](nmf_visnet* V) {
+    V->n_worlds = b->n_worlds;
+    return fill_visnet(V, p, types_host, neighbours_host, edges_host, taps_host, tap_w_host);
+  });
+}
+
+extern "C" void* nmf_visnet_field_ptr(nmf_visnet* V, int which, int32_t* width) {
+  if (!V) { fail("nmf_visnet_field_ptr: null handle"); return nullptr; }
+  const nmf::VisPtrs& P = V->ptrs;
+  const int C = V->args.n_types;
+  void* ptr[6] = {P.v, P.pooled, P.sums, P.signal, V->drive, P.fresh};
+  const int32_t w[6] = {2 * C * V->args.n_omm, 2 * C, 2 * C, 1, 2, 2};
+  if (which < 0 || which > 5) { fail("nmf_visnet_field_ptr: no such field"); return nullptr; }
+  if (width) *width = w[which];
+  return ptr[which];
+}
+
+// Pure stream-ordered work: two kernel launches.
+extern "C" int nmf_visnet_update(nmf_visnet* V, const float* omm_dev, const float* base_dev, float* drive_out_dev, void* stream) {
+  if (!V) return fail("nmf_visnet_update: null handle");
+  if (!omm_dev) return fail("nmf_visnet_update: null omm");
+  if (!drive_out_dev) return fail("nmf_visnet_update: null drive");
+  if (((uintptr_t)omm_dev & 7) || ((uintptr_t)base_dev & 3) || ((uintptr_t)drive_out_dev & 3))
+    return fail("nmf_visnet_update: omm must be 8-byte, base and drive 4-byte aligned");
+  DEVICE_GUARD(V);
+  hipLaunchKernelGGL(nmf::nmf_visnet_kernel, dim3(2u * (unsigned)V->n_worlds), dim3(V->threads), V->lds_bytes, (hipStream_t)stream,
+                     V->args, V->ptrs, V->taps, V->tables, reinterpret_cast<const float2*>(omm_dev));
+  HIP_OK(hipGetLastError());
+  hipLaunchKernelGGL(nmf::nmf_visnet_world_kernel, dim3((unsigned)((V->n_worlds + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     V->args, V->ptrs, base_dev, drive_out_dev);
   HIP_OK(hipGetLastError());
   return 0;
 }

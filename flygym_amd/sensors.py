@@ -18,15 +18,20 @@ names (``:199-200``) are not shipped, and no code exists, so the following is *b
   path-integration task — is stated in include/nmf.h and specified by tests/odometry_spec.py;
 * motion vision (:class:`MotionDetectors`) — two low-pass filters per ommatidium, a Hassenstein-Reichardt correlator per pair of
   neighbouring ommatidia (:meth:`Retina.motion_pairs`), wide-field flow per eye and an optomotor drive for the ``TurningCPG`` — is
-  stated in include/nmf.h and specified by tests/motion_spec.py; the reference holds no vision processing at all.
+  stated in include/nmf.h and specified by tests/motion_spec.py; the reference holds no vision processing at all;
+* a retinotopic visual network (:class:`RetinotopicNetwork`) — cell types as layers of one cell per ommatidium, joined by
+  convolution kernels on the hexagonal lattice (:meth:`Retina.hex_neighbours`), a leaky recurrent system whose pooled activity
+  steers the ``TurningCPG``; :func:`motion_pathway` is its default network — is stated in include/nmf.h and specified by
+  tests/visnet_spec.py.
 
 The arithmetic runs in ``libnmf_hip.so`` (``nmf_retina_resample``, ``nmf_odor_intensity``, ``nmf_plume_*``, ``nmf_odometry_*``,
-``nmf_motion_*``).
+``nmf_motion_*``, ``nmf_visnet_*``).
 """
 
 from __future__ import annotations
 
 import ctypes
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -34,7 +39,8 @@ from . import _native
 from ._handle import NativeHandle, _field_view, check_params, fly_batch, leg_segments, reset_mask, site_arrays
 from .anatomy import LEGS
 
-__all__ = ["Retina", "OdorSensors", "OdorPlume", "PathIntegrator", "MotionDetectors", "RAW_IMG_HEIGHT", "RAW_IMG_WIDTH", "NUM_OMMATIDIA"]
+__all__ = ["Retina", "OdorSensors", "OdorPlume", "PathIntegrator", "MotionDetectors", "RetinotopicNetwork", "VisualNetwork", "FlatNetwork", "motion_pathway",
+           "flatten_network", "eye_tables", "RAW_IMG_HEIGHT", "RAW_IMG_WIDTH", "NUM_OMMATIDIA"]
 
 RAW_IMG_HEIGHT = 512     # flygym1_config.yaml:143
 RAW_IMG_WIDTH = 450      # :144
@@ -47,6 +53,8 @@ EYE_CAMERAS = {          # :164-173  (parent segment, offset mm, euler orientati
 MAX_STEERING_SIDE = 2047          # csrc/nmf_taxis.hip: ommatidium centres are int16 sixteenths of a pixel ...
 MAX_STEERING_OMMATIDIA = 1024     # ... and at most kMaxOmmatidia of them are summed
 MAX_MOTION_PAIRS = 3072           # csrc/nmf_motion.hip: pairs of neighbouring ommatidia an eye's int32 flow sums can hold
+MAX_VISNET_TYPES, MAX_VISNET_CELLS, MAX_VISNET_TABLE = 32, 24576, 19      # csrc/nmf_visnet.hip: what one CU's LDS holds ...
+MAX_VISNET_EDGES, MAX_VISNET_TAPS, MAX_VISNET_SUBSTEPS = 512, 4096, 8     # ... and the limits of include/nmf.h
 ODOR_SENSOR_SITES = [    # :175-192  (parent segment, offset in the segment frame, mm)
     ("c_rostrum", (-0.15, 0.15, -0.15)),     # left maxillary palp
     ("c_rostrum", (-0.15, -0.15, -0.15)),    # right maxillary palp
@@ -175,6 +183,62 @@ class Retina:
             raise ValueError(f"{a.size} pairs within {reach} pitches exceed the motion kernel's {MAX_MOTION_PAIRS}")
         weights = v[a, b] / dist[a, b, None]
         return np.stack([a, b], axis=-1).astype(np.int32), weights.astype(np.float32)
+
+    def hex_neighbours(self, rings: int = 2):
+        """``(neighbours (T, num_ommatidia) int32, offsets (T, 2) float64)``, ``T`` = 1, 7 or 19 for ``rings`` = 0, 1, 2: the
+        hexagonal lattice of the retina as a table, the taps a :class:`RetinotopicNetwork` convolves over.  ``offsets[t]`` is a
+        lattice vector in image coordinates (x = column, y = row) and ``neighbours[t, i]`` the ommatidium whose centre lies within
+        a quarter of a pitch of ``centre_i + offsets[t]``, or -1 where the retina ends.
+
+        Derived from :meth:`ommatidia_centres`: the displacements from the ommatidium nearest the centroid to its six nearest
+        neighbours give the pitch (their mean length) and two lattice vectors 60 degrees apart; the taps are their integer
+        combinations within 2.05 pitches of zero — tap 0 the cell itself, then the classes at distance 1, sqrt(3) and 2 pitches,
+        each in ascending ``atan2(dy, dx)``.  ``rings`` = 1 keeps the first class, 2 all three.  The default retina: 690
+        ommatidia have any one distance-1 tap, 660 a distance-sqrt(3) tap and 659 a distance-2 tap; 547 have all 19.
+
+        Refuses (``ValueError``) more than 1024 ommatidia, fewer than 7 when ``rings`` > 0, and a retina that is not a hexagonal
+        lattice: the combinations do not fall into classes of six at 1, sqrt(3) and 2 pitches, or a target has an ommatidium
+        between 0.25 and 0.75 pitch from it."""
+        if rings not in (0, 1, 2):
+            raise ValueError(f"rings must be 0, 1 or 2, got {rings!r}")
+        n = self.num_ommatidia
+        if n > MAX_STEERING_OMMATIDIA:
+            raise ValueError(f"a retina of {n} ommatidia exceeds the network kernel's {MAX_STEERING_OMMATIDIA}")
+        if rings == 0:
+            return np.arange(n, dtype=np.int32)[None, :].copy(), np.zeros((1, 2))
+        if n < 7:
+            raise ValueError(f"a retina of {n} ommatidia has no hexagonal neighbourhood (rings > 0 needs at least 7)")
+        c = self.ommatidia_centres()
+        middle = int(np.argmin(np.hypot(*(c - c.mean(axis=0)).T)))
+        d = c - c[middle]
+        six = d[np.argsort(np.hypot(d[:, 0], d[:, 1]), kind="stable")[1:7]]
+        pitch = float(np.hypot(six[:, 0], six[:, 1]).mean())
+        angle = np.arctan2(six[:, 1], six[:, 0])
+        first = int(np.argmin(angle))
+        turn = (angle - angle[first]) % (2.0 * np.pi)
+        at = lambda want: six[int(np.argmin(np.abs(turn - want)))]             # the neighbour `want` radians on from the first
+        a, b = 0.5 * (at(0.0) - at(np.pi)), 0.5 * (at(np.pi / 3.0) - at(4.0 * np.pi / 3.0))      # (each with its opposite)
+        grid = np.array([(m, k) for m in range(-3, 4) for k in range(-3, 4)], dtype=np.float64)
+        points = grid[:, :1] * a + grid[:, 1:] * b
+        dist = np.hypot(points[:, 0], points[:, 1]) / pitch
+        points, dist = points[dist < 2.05], dist[dist < 2.05]
+        classes = [points[np.abs(dist - want) < 0.1] for want in (0.0, 1.0, np.sqrt(3.0), 2.0)]
+        if [len(k) for k in classes] != [1, 6, 6, 6] or len(points) != 19:
+            raise ValueError("the retina is not a hexagonal lattice: the neighbours of its middle ommatidium do not span one")
+        offsets = np.concatenate([k[np.argsort(np.arctan2(k[:, 1], k[:, 0]), kind="stable")] for k in classes])
+        offsets[0] = 0.0
+        offsets = offsets[:7] if rings == 1 else offsets
+        neighbours = np.full((len(offsets), n), -1, dtype=np.int32)
+        for t, off in enumerate(offsets):
+            target = c + off
+            gap = np.hypot(target[:, None, 0] - c[None, :, 0], target[:, None, 1] - c[None, :, 1]) / pitch        # [i, j]
+            if ((gap >= 0.25) & (gap < 0.75)).any():
+                i, j = np.argwhere((gap >= 0.25) & (gap < 0.75))[0]
+                raise ValueError(f"the retina is not a hexagonal lattice: ommatidium {j} lies {gap[i, j]:.2f} pitch from tap {t} of ommatidium {i}")
+            j = gap.argmin(axis=1)
+            hit = gap[np.arange(n), j] < 0.25
+            neighbours[t, hit] = j[hit]
+        return neighbours, offsets
 
     def hex_pxls_to_human_readable(self, readings: np.ndarray) -> np.ndarray:
         """Paint ``(num_ommatidia, 2)`` readings back onto the pixel grid (for inspection)."""
@@ -616,3 +680,291 @@ class MotionDetectors(NativeHandle):
         h = self._handle()
         m = reset_mask(mask, self.n_worlds, self.sim)
         _native.check(_native.lib().nmf_motion_reset(h, None if m is None else m.data_ptr(), self.sim._stream()))
+
+
+@dataclass
+class VisualNetwork:
+    """A retinotopic network for :class:`RetinotopicNetwork`, by name: ``types`` the cell types in the order of the views; ``tau``
+    (seconds, every type), ``bias``, ``in_w`` (a pair: the weights of the two reading channels) and ``steer_w`` per type name
+    (missing: 0); ``edges`` a list of ``(post, pre, {tap: weight})`` with ``tap`` a row of the neighbour table
+    (:meth:`Retina.hex_neighbours`).  The taps of an edge are taken in the dict's order, the edges into a type in the list's."""
+
+    types: tuple
+    tau: dict
+    bias: dict = field(default_factory=dict)
+    in_w: dict = field(default_factory=dict)
+    steer_w: dict = field(default_factory=dict)
+    edges: list = field(default_factory=list)
+
+
+@dataclass
+class FlatNetwork:
+    """A network for :class:`RetinotopicNetwork` by index, as ``nmf_visnet_create`` takes it — for networks a program builds:
+    ``types`` the names, ``tau``, ``bias``, ``steer_w`` ``(C,)`` and ``in_w`` ``(C, 2)`` arrays, ``edges`` ``(E, 2)`` int (post,
+    pre), ``taps`` ``(K, 2)`` int (edge, tap) in any order — the taps of one edge keep their order among themselves, a tap may
+    repeat — and ``tap_w`` ``(K,)``."""
+
+    types: tuple
+    tau: np.ndarray
+    bias: np.ndarray
+    in_w: np.ndarray
+    steer_w: np.ndarray
+    edges: np.ndarray
+    taps: np.ndarray
+    tap_w: np.ndarray
+
+
+def _flatten_arrays(net: FlatNetwork, dt: float, substeps: int):
+    names = tuple(net.types)
+    C = len(names)
+    tau = np.asarray(net.tau, dtype=np.float64).reshape(-1)
+    edges, taps = np.asarray(net.edges).reshape(-1, 2), np.asarray(net.taps).reshape(-1, 2)
+    tap_w = np.asarray(net.tap_w, dtype=np.float32).reshape(-1)
+    columns = [np.asarray(net.bias, dtype=np.float32).reshape(-1), *np.asarray(net.in_w, dtype=np.float32).reshape(-1, 2).T,
+               np.asarray(net.steer_w, dtype=np.float32).reshape(-1)]
+    if C < 1 or tau.shape != (C,) or any(col.shape != (C,) for col in columns) or len(tap_w) != len(taps):
+        raise ValueError(f"a flat network of {C} types needs tau, bias and steer_w of shape ({C},), in_w ({C}, 2) and a weight per tap")
+    if not (np.issubdtype(edges.dtype, np.integer) or edges.size == 0) or not (np.issubdtype(taps.dtype, np.integer) or taps.size == 0):
+        raise ValueError("edges and taps hold integer indices")
+    if edges.size and (edges.min() < 0 or edges.max() >= C):
+        raise ValueError(f"an edge names a type outside 0..{C - 1}")
+    if taps.size and (taps[:, 0].min() < 0 or taps[:, 0].max() >= len(edges)):
+        raise ValueError(f"a tap belongs to an edge outside 0..{len(edges) - 1}")
+    if not (dt > 0 and (tau > 0).all()):
+        raise ValueError(f"dt and every tau must be positive, got dt = {dt!r}, tau = {tau.tolist()}")
+    a = (1.0 - np.exp(-np.float64(dt) / (int(substeps) * tau))).astype(np.float32)
+    types = np.ascontiguousarray(np.stack([columns[0], columns[1], columns[2], a, columns[3]], axis=-1), dtype=np.float32)
+    return names, types, np.ascontiguousarray(edges, dtype=np.int32), np.ascontiguousarray(taps, dtype=np.int32), np.ascontiguousarray(tap_w)
+
+
+def flatten_network(network, dt: float, substeps: int = 1):
+    """``network`` (a :class:`VisualNetwork` or a dict of its fields) as the arrays of ``nmf_visnet_create``: ``(names, types
+    (C, 5) float32 — bias, in_w[0], in_w[1], a, steer_w — edges (E, 2) int32 (post, pre), taps (K, 2) int32 (edge, tap), tap_w
+    (K,) float32)`` with ``a = float32(1 - exp(-dt / (substeps tau)))`` computed in float64."""
+    if isinstance(network, FlatNetwork):
+        return _flatten_arrays(network, dt, substeps)
+    net = VisualNetwork(**network) if isinstance(network, dict) else network
+    names = tuple(net.types)
+    if len(set(names)) != len(names) or not names:
+        raise ValueError("a network needs at least one cell type, each named once")
+    index = {name: c for c, name in enumerate(names)}
+    for label, table in (("tau", net.tau), ("bias", net.bias), ("in_w", net.in_w), ("steer_w", net.steer_w)):
+        unknown = [k for k in table if k not in index]
+        if unknown:
+            raise ValueError(f"{label} names the unknown cell type {unknown[0]!r}")
+    missing = [name for name in names if name not in net.tau]
+    if missing:
+        raise ValueError(f"cell type {missing[0]!r} has no tau")
+    tau = np.array([net.tau[name] for name in names], dtype=np.float64)
+    if not (dt > 0 and (tau > 0).all()):
+        raise ValueError(f"dt and every tau must be positive, got dt = {dt!r}, tau = {tau.tolist()}")
+    types = np.zeros((len(names), 5), dtype=np.float32)
+    types[:, 0] = [net.bias.get(name, 0.0) for name in names]
+    types[:, 1:3] = [net.in_w.get(name, (0.0, 0.0)) for name in names]
+    types[:, 3] = (1.0 - np.exp(-np.float64(dt) / (int(substeps) * tau))).astype(np.float32)
+    types[:, 4] = [net.steer_w.get(name, 0.0) for name in names]
+    edges, taps, tap_w = [], [], []
+    for e, (post, pre, kernel) in enumerate(net.edges):
+        if post not in index or pre not in index:
+            raise ValueError(f"edge {e} = ({post!r}, {pre!r}) names an unknown cell type")
+        edges.append((index[post], index[pre]))
+        for tap, weight in kernel.items():
+            taps.append((e, int(tap)))
+            tap_w.append(weight)
+    return (names, types, np.array(edges, dtype=np.int32).reshape(-1, 2), np.array(taps, dtype=np.int32).reshape(-1, 2),
+            np.array(tap_w, dtype=np.float32))
+
+
+MOTION_DIRECTIONS = {"ftb": (1.0, 0.0), "btf": (-1.0, 0.0), "down": (0.0, 1.0), "up": (0.0, -1.0)}
+
+
+def motion_pathway(offsets=None) -> VisualNetwork:
+    """The build-defined default network of :class:`RetinotopicNetwork`: an elementary-motion-detector pathway of 15 cell types
+    per eye.  Pinned by nothing; the values below come from the grating runs of tests/test_visnet_cpu.py.
+
+    ``Lm``  (tau 200 ms, in_w (1, 1)): the local mean luminance.
+    ``On``  (tau 5 ms, in_w (1, 1), -1 ``Lm`` at tap 0) and ``Off`` (tau 5 ms, in_w (-1, -1), +1 ``Lm``): the rectified brightening
+            and darkening of a cell against its mean.
+    ``OnF`` (tau 8 ms) and ``OnD`` (tau 60 ms), each +1 ``On`` at tap 0; ``OffF`` and ``OffD`` likewise: a fast and a delayed copy.
+    ``T4ftb``, ``T4btf``, ``T4down``, ``T4up`` (tau 10 ms, bias -0.05): the ON cells that prefer motion along +x, -x, +y, -y of the
+            lattice; ``T5...`` the OFF ones.  Each sums +1 of its pathway's fast type at tap 0, +1.5 of the delayed type spread
+            over the distance-1 taps on the side the motion comes from (tap ``t`` in proportion to how far ``offsets[t]`` lies
+            along that direction) and -1.5 of the delayed type spread likewise over the taps on the side it goes to.
+    ``steer_w``: +1 for the ``ftb`` types and -1 for the ``btf`` types.  With the class's default tables +x of the lattice runs from
+            front to back across either eye, so the signal is the front-to-back motion of the left eye minus the right eye's: the
+            rotation of the panorama, positive counter-clockwise, as ``MotionDetectors.rotation``.
+
+    ``offsets``: the lattice vectors of the distance-1 taps, rows 1..6 of ``Retina.hex_neighbours(...)[1]`` (default: the default
+    retina's)."""
+    off = np.asarray(Retina().hex_neighbours(1)[1] if offsets is None else offsets, dtype=np.float64)[:7]
+    if off.shape != (7, 2):
+        raise ValueError(f"offsets must hold the cell itself and its six distance-1 taps, got shape {off.shape}")
+    pitch = np.hypot(off[1:, 0], off[1:, 1]).mean()
+    types = ["Lm", "On", "Off", "OnF", "OnD", "OffF", "OffD"]
+    tau = dict(Lm=0.2, On=0.005, Off=0.005, OnF=0.008, OnD=0.06, OffF=0.008, OffD=0.06)
+    in_w = dict(Lm=(1.0, 1.0), On=(1.0, 1.0), Off=(-1.0, -1.0))
+    edges = [("On", "Lm", {0: -1.0}), ("Off", "Lm", {0: 1.0}), ("OnF", "On", {0: 1.0}), ("OnD", "On", {0: 1.0}),
+             ("OffF", "Off", {0: 1.0}), ("OffD", "Off", {0: 1.0})]
+    bias, steer_w = {}, {}
+    for cell, path in (("T4", "On"), ("T5", "Off")):
+        for name, u in MOTION_DIRECTIONS.items():
+            along = off @ np.asarray(u) / pitch                                    # how far each tap lies along the motion
+            behind, ahead = {}, {}
+            for t in range(1, 7):
+                if along[t] < -0.25:
+                    behind[t] = -along[t]
+                elif along[t] > 0.25:
+                    ahead[t] = along[t]
+            kind = cell + name
+            types.append(kind)
+            tau[kind], bias[kind] = 0.01, -0.05
+            edges.append((kind, path + "F", {0: 1.0}))
+            edges.append((kind, path + "D", {**{t: 1.5 * w / sum(behind.values()) for t, w in behind.items()},
+                                             **{t: -1.5 * w / sum(ahead.values()) for t, w in ahead.items()}}))
+            if name in ("ftb", "btf"):
+                steer_w[kind] = 1.0 if name == "ftb" else -1.0
+    return VisualNetwork(types=tuple(types), tau=tau, bias=bias, in_w=in_w, steer_w=steer_w, edges=edges)
+
+
+def eye_tables(retina, rings: int = 2, front_edge=None):
+    """``(neighbours (2, T, n_omm) int32, offsets (T, 2) float64)``: ``retina.hex_neighbours(rings)`` per eye, with the rows of an
+    eye whose image has its LAST column facing forward (``front_edge[eye]`` = 1, ``controllers.eye_front_edges``) exchanged so
+    that row ``t`` is the tap at ``offsets[t]`` mirrored in x.  Lattice +x then runs from front to back across either eye, and a
+    cell type means the same direction about the fly in both.  Needs a lattice that its mirror image maps onto itself."""
+    from .controllers import eye_front_edges
+
+    front = eye_front_edges() if front_edge is None else tuple(front_edge)
+    table, offsets = retina.hex_neighbours(rings)
+    pitch = float(np.hypot(offsets[1:, 0], offsets[1:, 1]).min()) if len(offsets) > 1 else 1.0
+    mirrored = offsets * np.array([-1.0, 1.0])
+    gap = np.hypot(mirrored[:, None, 0] - offsets[None, :, 0], mirrored[:, None, 1] - offsets[None, :, 1]) / pitch
+    swap = gap.argmin(axis=1)
+    if (gap[np.arange(len(offsets)), swap] > 0.1).any():
+        raise ValueError("the retina's lattice is not its own mirror image in x: pass neighbours of shape (2, T, n_omm)")
+    return np.stack([table[swap] if front[eye] else table for eye in range(2)]).astype(np.int32), offsets
+
+
+class _VisnetParams(ctypes.Structure):
+    """``nmf_visnet_params`` of include/nmf.h."""
+
+    _fields_ = [("n_types", ctypes.c_int32), ("n_omm", ctypes.c_int32), ("n_table", ctypes.c_int32), ("n_edges", ctypes.c_int32),
+                ("n_taps", ctypes.c_int32), ("substeps", ctypes.c_int32), ("gain", ctypes.c_float), ("delta", ctypes.c_float),
+                ("base", ctypes.c_float), ("drive_min", ctypes.c_float), ("drive_max", ctypes.c_float)]
+
+
+class RetinotopicNetwork(NativeHandle):
+    """A retinotopic visual network on the GPU (``nmf_visnet_*``, ``csrc/nmf_visnet.hip``): cell types that are layers of one cell
+    per ommatidium, joined by small convolution kernels on the retina's hexagonal lattice and integrated as a leaky recurrent
+    system, in the manner of Lappalainen et al. 2024 — the kind of network flygym 1.x's "advanced vision" task reads.  The pooled
+    activity of the types, not the image, steers the ``TurningCPG``.
+
+    Build-defined (the reference ships no vision processing) and pinned by nothing; the statement of the model is include/nmf.h
+    (``nmf_visnet_update``), its specification in numpy tests/visnet_spec.py, which the kernel equals bit for bit.  One
+    :meth:`update` per control tick, from the ommatidia readings of both eyes (``EyeRenderer.render_into``); per eye, ``substeps``
+    times with the same readings ``x0_i, x1_i`` (the two channels of ommatidium ``i``)::
+
+        r[c][i] = max(v[c][i], 0)                                            of the old state of every type
+        s = bias_c + in_w[c][0] x0_i + in_w[c][1] x1_i + sum over the taps (pre, t, w) into c of  w r[pre][neighbours[t][i]]
+        v[c][i] += a_c (s - v[c][i])                                         a_c = 1 - exp(-dt / (substeps tau_c))
+    then
+        pooled[c] = mean_i min(r[c][i], 4)                                   each term rounded to 2^-16, summed as integers
+        signal = sum_c steer_w_c (pooled[left][c] - pooled[right][c])
+        g = gain signal;  q = g / (1 + |g|);  o_left = 1 - delta max(q, 0);  o_right = 1 - delta max(-q, 0)
+        drive[side] = clip(base[side] o_side, drive_min, drive_max)          (side 0 = left, as ``TurningCPG.drive``)
+
+    a tap on a missing neighbour reads 0, and a world's first update starts from ``v[c][i] = bias_c``.
+
+    Args:
+        sim: the batch; a world with several flies resolves to ``sim.for_fly(fly_name)``.
+        fly_name: the fly whose eyes are read.
+        network: a :class:`VisualNetwork` (or a dict of its fields) or a :class:`FlatNetwork`; :func:`motion_pathway` is the build-defined default.  At most
+            32 types, 24576 cells (types x ommatidia), 512 edges and 4096 taps.
+        dt: the control tick, seconds between two updates.
+        retina: the retina whose readings :meth:`update` takes (default: the default :class:`Retina`); at most 1024 ommatidia.
+        neighbours: the neighbour table, ``(T, n_omm)`` for both eyes or ``(2, T, n_omm)`` per eye, ``T`` in 1..19, entries in
+            -1..n_omm-1.  Default: :func:`eye_tables` of ``retina`` — the left eye's lattice mirrored, so that +x of the lattice
+            runs from front to back across both eyes — with as many rings (0, 1 or 2: 1, 7 or 19 rows) as the network's taps reach.
+        substeps: 1..8 repetitions of the rule per update.
+        gain: the signal at which a side is slowed by ``delta / 2`` is ``1 / gain``.  The default of 10 is not tuned in closed
+            loop: a full-field grating of contrast 0.4 drifting at 2 Hz gives ``motion_pathway`` a signal of 0.21.
+        delta: the largest share a side is slowed by; 0 switches the steering off (the drive is ``base``).
+        base: the drive without a signal (or pass a tensor to :meth:`update`).
+
+    ``v`` ``(n, 2, C, n_omm)``, ``pooled`` ``(n, 2, C)``, ``signal`` ``(n,)``, ``drive`` ``(n, 2)`` float32, ``sums`` ``(n, 2, C)``
+    int32 and ``fresh`` ``(n, 2)`` uint8 are zero-copy views of the handle's device memory, allocated once; ``type_names`` names
+    the ``C`` axis.  Every method is stream-ordered device work on the simulation's stream; :meth:`update` is two launches, allocates
+    nothing and can be captured in a graph.  Close it before its simulation.
+    """
+
+    _destroy_entry, _noun = "nmf_visnet_destroy", "visual network"
+    _views = ("v", "pooled", "sums", "signal", "drive", "fresh")
+
+    def __init__(self, sim, fly_name: str, network, *, dt: float, retina=None, neighbours=None, substeps: int = 1, gain: float = 10.0,
+                 delta: float = 0.8, base: float = 1.0, drive_min: float = 0.2, drive_max: float = 1.2):
+        sim = fly_batch(sim, fly_name, resolve=True)
+        if fly_name not in sim.world.fly_lookup:
+            raise ValueError(f"no fly named {fly_name!r} in this simulation ({', '.join(sim.world.fly_lookup)})")
+        if int(substeps) != substeps or not 1 <= substeps <= MAX_VISNET_SUBSTEPS:
+            raise ValueError(f"substeps must be in 1..{MAX_VISNET_SUBSTEPS}, got {substeps!r}")
+        self.sim, self.fly_name = sim, fly_name
+        self.retina = retina or Retina()
+        self.n_worlds, self.n_omm = int(sim.n_worlds), int(self.retina.num_ommatidia)
+        if self.n_omm > MAX_STEERING_OMMATIDIA:
+            raise ValueError(f"a retina of {self.n_omm} ommatidia exceeds the network kernel's {MAX_STEERING_OMMATIDIA}")
+        self.dt, self.substeps = float(dt), int(substeps)
+        self.type_names, self.types, self.edges, self.taps, self.tap_w = flatten_network(network, self.dt, self.substeps)
+        C = self.n_types = len(self.type_names)
+        if C > MAX_VISNET_TYPES or C * self.n_omm > MAX_VISNET_CELLS:
+            raise ValueError(f"{C} types x {self.n_omm} ommatidia exceed the network kernel's {MAX_VISNET_TYPES} types or {MAX_VISNET_CELLS} cells")
+        if len(self.edges) > MAX_VISNET_EDGES or len(self.taps) > MAX_VISNET_TAPS:
+            raise ValueError(f"{len(self.edges)} edges and {len(self.taps)} taps exceed the network kernel's {MAX_VISNET_EDGES} edges or {MAX_VISNET_TAPS} taps")
+        if neighbours is None:                               # the smallest table that holds every tap the network reads
+            reach = int(self.taps[:, 1].max()) if len(self.taps) else 0
+            nb = eye_tables(self.retina, 0 if reach == 0 else 1 if reach < 7 else 2)[0]
+        else:
+            nb = np.asarray(neighbours)
+        if nb.ndim == 2:
+            nb = np.stack([nb, nb])
+        if nb.ndim != 3 or nb.shape[0] != 2 or not 1 <= nb.shape[1] <= MAX_VISNET_TABLE or nb.shape[2] != self.n_omm or not np.issubdtype(nb.dtype, np.integer):
+            raise ValueError(f"neighbours takes an int table of shape (T, {self.n_omm}) or (2, T, {self.n_omm}) with T in 1..{MAX_VISNET_TABLE}, got {nb.shape} {nb.dtype}")
+        if nb.min() < -1 or nb.max() >= self.n_omm:
+            raise ValueError(f"a neighbour lies outside -1..{self.n_omm - 1}")
+        self.neighbours = np.ascontiguousarray(nb, dtype=np.int32)
+        if len(self.taps) and (self.taps[:, 1].min() < 0 or self.taps[:, 1].max() >= nb.shape[1]):
+            raise ValueError(f"a tap reads a row outside the neighbour table's {nb.shape[1]}")
+        if not np.isfinite(self.types).all() or not np.isfinite(self.tap_w).all():
+            raise ValueError("a bias, weight or coefficient of the network is not finite")
+        check_params(_VisnetParams, "nmf_visnet_params_size", "sensors.py")
+        self._params = _VisnetParams(C, self.n_omm, int(nb.shape[1]), len(self.edges), len(self.taps), self.substeps, float(gain),
+                                     float(delta), float(base), float(drive_min), float(drive_max))
+        h = self._create("nmf_visnet_create", sim._batch_h, ctypes.byref(self._params), self.types.ctypes.data, self.neighbours.ctypes.data,
+                         self.edges.ctypes.data if len(self.edges) else None, self.taps.ctypes.data if len(self.taps) else None,
+                         self.tap_w.ctypes.data if len(self.taps) else None)
+        n = self.n_worlds
+        view = lambda which, shape, typestr="<f4": _field_view(sim, _native.lib().nmf_visnet_field_ptr, h, which, typestr, shape)
+        self.v, self.pooled, self.sums = view(0, (n, 2, C, self.n_omm)), view(1, (n, 2, C)), view(2, (n, 2, C), "<i4")
+        self.signal, self.drive, self.fresh = view(3, (n,)), view(4, (n, 2)), view(5, (n, 2), "|u1")
+
+    _checked = MotionDetectors._checked
+
+    def update(self, omm, base=None, out=None):
+        """One update from ``omm`` ``(n_worlds, 2, num_ommatidia, 2)`` (float32, contiguous, on the simulation's device): two kernel
+        launches on the simulation's stream, no allocation — capturable.  Advances :attr:`v`, writes :attr:`sums`, :attr:`pooled`
+        and :attr:`signal`, and the drive into ``out`` ``(n_worlds, 2)`` (for example ``cpg.drive``) or into :attr:`drive`; returns
+        the drive tensor.  ``base`` ``(n_worlds, 2)`` (for example ``MotionDetectors.drive``) takes the place of the scalar
+        parameter ``base``."""
+        h, n = self._handle(), self.n_worlds
+        self._checked("omm", omm, (n, 2, self.n_omm, 2))
+        if base is not None:
+            self._checked("base", base, (n, 2))
+        drive = self.drive if out is None else self._checked("out", out, (n, 2))
+        _native.check(_native.lib().nmf_visnet_update(h, omm.data_ptr(), None if base is None else base.data_ptr(), drive.data_ptr(),
+                                                      self.sim._stream()))
+        return drive
+
+    def reset(self, mask=None) -> None:
+        """The worlds of ``mask`` (``(n_worlds,)`` bool, numpy or torch; default all) forget their state: their next update starts
+        from ``v = bias``, as a first update does.  The others keep theirs."""
+        h = self._handle()
+        m = reset_mask(mask, self.n_worlds, self.sim)
+        _native.check(_native.lib().nmf_visnet_reset(h, None if m is None else m.data_ptr(), self.sim._stream()))

@@ -33,6 +33,7 @@ typedef struct nmf_motion nmf_motion;
 typedef struct nmf_navigator nmf_navigator;
 typedef struct nmf_stabilizer nmf_stabilizer;
 typedef struct nmf_rules nmf_rules;
+typedef struct nmf_visnet nmf_visnet;
 
 /* Per-world fields addressable through nmf_field_ptr / nmf_gather_* */
 enum nmf_field {
@@ -740,6 +741,86 @@ int nmf_motion_update(nmf_motion* motion, const float* omm_dev, const float* bas
 #define NMF_MOTION_DRIVE 6        /* [2] float32: a drive buffer of the handle's own (starts at 1)             */
 #define NMF_MOTION_FRESH 7        /* [1] uint8                                                                 */
 void* nmf_motion_field_ptr(nmf_motion* motion, int which, int32_t* width);
+
+/* A retinotopic visual network with its state on the device (flygym_amd.sensors.RetinotopicNetwork; csrc/nmf_visnet.hip): cell
+ * types that are layers of one cell per ommatidium, joined by small convolution kernels on the hexagonal lattice of the retina and
+ * integrated as a leaky recurrent system, in the manner of Lappalainen et al. 2024 as flygym 1.x's "advanced vision" task reads it;
+ * the pooled activity of the types, not the image, drives the CPG.  No reference counterpart (the snapshot holds no vision
+ * processing): build-defined and pinned by nothing (specification tests/visnet_spec.py).
+ * Shared by all worlds of a handle: C cell types, per type c the float32 constants bias_c, in_w[c][0..1], a_c, steer_w_c; a
+ * neighbour table neighbours[2][T][n_omm] int32 per eye (row t: the ommatidium that lies at lattice offset t from ommatidium i, or
+ * -1; see Retina.hex_neighbours; the two eyes' tables differ where the caller mirrors one eye's lattice so that an offset means
+ * the same direction about the fly in both); E edges (post, pre) between types; and a flat tap list, tap k = (edge, t, w) with t a row of the table.
+ * State per world and eye: a "fresh" byte and v[c][i] float32, one cell per type and ommatidium.  One update (at most two launches
+ * per control tick), per world and eye e (0 left, 1 right), from omm[w][e][i][2]:
+ *   x0_i = omm[i][0], x1_i = omm[i][1];  if the eye is fresh: v[c][i] = bias_c
+ *   `substeps` times, every type from the OLD state of every type (synchronous):
+ *     r[c][i] = v[c][i] > 0 ? v[c][i] : +0
+ *     s = bias_c;  s = fmaf(in_w[c][0], x0_i, s);  s = fmaf(in_w[c][1], x1_i, s)
+ *     for the edges into c in the caller's order, for the taps of each edge in the caller's order:
+ *       j = neighbours[e][t][i];  s = fmaf(w, j >= 0 ? r[pre][j] : +0, s)     (a missing neighbour still executes its fmaf)
+ *     v[c][i] <- v[c][i] + fl(a_c fl(s - v[c][i]))
+ *   S[c] = sum_i (int32) rint(min(r[c][i], 4) 65536) of the NEW state
+ *       (terms of resolution 2^-16 in [0, 4]: with n_omm <= 1024 a sum stays below 2^29, and integer sums do not depend on the
+ *        order of the reduction)
+ *   pooled[c] = S[c] / (65536 n_omm)       (the correctly rounded float64 division of the exact operands, rounded once to float32)
+ *   the eye is no longer fresh
+ * and per world:
+ *   t = +0;  for c ascending: t = fmaf(steer_w_c, fl(pooled[0][c] - pooled[1][c]), t)          (a zero is +0: the signal)
+ *   g = gain t;  q = g / (1 + |g|) (correctly rounded as above);  o_0 = 1 - delta max(q, 0), o_1 = 1 - delta max(-q, 0)
+ *   drive[side] = min(max(base[side] o_side, drive_min), drive_max)      (side 0 = left: the order of NMF_CPG_DRIVE; base[side]
+ *                                                                         from base_dev, or the parameter `base` without it)
+ * Every float32 operation is rounded as written (no contraction, no reassociation, an fmaf where one is written): state and outputs
+ * equal the specification's bit for bit.  a_c is 1 - exp(-dt / (substeps tau_c)) of the caller's control tick dt, computed in
+ * float64 on the host and rounded once to float32. */
+#define NMF_VISNET_MAX_TYPES 32       /* C                                                      */
+#define NMF_VISNET_MAX_CELLS 24576    /* C x n_omm: 96 KiB of state, held in one CU's LDS       */
+#define NMF_VISNET_MAX_TABLE 19       /* T: the lattice points within two pitches               */
+#define NMF_VISNET_MAX_EDGES 512      /* E                                                      */
+#define NMF_VISNET_MAX_TAPS 4096      /* taps of all edges together                             */
+#define NMF_VISNET_MAX_SUBSTEPS 8
+typedef struct nmf_visnet_params {
+  int32_t n_types, n_omm, n_table, n_edges, n_taps;      /* C, ommatidia per eye, T, E, taps in all                        */
+  int32_t substeps;                                      /* 1..8 repetitions of the rule per update                        */
+  float gain, delta;                                     /* optomotor rule: g = gain t; a side is slowed by at most delta  */
+  float base, drive_min, drive_max;
+} nmf_visnet_params;
+
+/* sizeof(nmf_visnet_params) as this library was compiled (as nmf_eye_params_size). */
+size_t nmf_visnet_params_size(void);
+
+/* An explicit handle for the worlds of `batch`, on its device.  HOST memory, copied: types_host[C][5] float32 (bias, in_w[0],
+ * in_w[1], a, steer_w per type), neighbours_host[2][T][n_omm] int32, edges_host[E][2] int32 (post, pre), taps_host[n_taps][2] int32
+ * (edge, t) and tap_w_host[n_taps] float32 (the last three may be NULL when their count is 0).  Owns the network, the state and the
+ * outputs; every world starts fresh.  NOT stream-ordered (allocations, synchronous uploads); must not be called inside a stream
+ * capture.  NULL on error (nmf_last_error names the offending entry), with nothing left allocated: n_types outside 1..32; n_omm
+ * outside 1..1024; n_types x n_omm above 24576; n_table outside 1..19; n_edges outside 0..512; n_taps outside 0..4096; substeps
+ * outside 1..8; a constant, weight or parameter that is not finite; a_c outside (0, 1]; a neighbour outside -1..n_omm-1; an edge
+ * whose types lie outside 0..C-1; a tap whose edge lies outside 0..E-1 or whose t lies outside 0..T-1; no device memory. */
+nmf_visnet* nmf_visnet_create(nmf_batch* batch, const nmf_visnet_params* params, const float* types_host,
+                              const int32_t* neighbours_host, const int32_t* edges_host, const int32_t* taps_host,
+                              const float* tap_w_host);
+void nmf_visnet_destroy(nmf_visnet* visnet);
+
+/* Both eyes of the worlds with mask_dev[w] != 0 (uint8 per world, device memory; NULL: all) become fresh: their next update
+ * starts from v[c][i] = bias_c, exactly as a first update does.  The others are not touched.  Stream-ordered. */
+int nmf_visnet_reset(nmf_visnet* visnet, const uint8_t* mask_dev, void* stream);
+
+/* One update of every world from omm_dev[n_worlds][2][n_omm][2] float32 (8-byte aligned): argument checks and TWO kernel launches
+ * on `stream` (the network per world and eye, then signal and drive per world), no allocation, no host synchronisation,
+ * hipGraph-capturable (the fresh bytes live on the device, so a captured update replays correctly).  base_dev[n_worlds][2] float32
+ * or NULL (the parameter `base`); the drive goes to drive_out_dev[n_worlds][2] float32 (for example NMF_CPG_DRIVE, or the
+ * handle's own NMF_VISNET_DRIVE).  Refused: a null handle, omm or drive; a misaligned buffer. */
+int nmf_visnet_update(nmf_visnet* visnet, const float* omm_dev, const float* base_dev, float* drive_out_dev, void* stream);
+
+/* Device pointer + row width of an array of the handle (zero-copy views; writable between launches). */
+#define NMF_VISNET_V 0            /* [2][C][n_omm] float32                                                     */
+#define NMF_VISNET_POOLED 1       /* [2][C] float32                                                            */
+#define NMF_VISNET_SUMS 2         /* [2][C] int32                                                              */
+#define NMF_VISNET_SIGNAL 3       /* [1] float32                                                               */
+#define NMF_VISNET_DRIVE 4        /* [2] float32: a drive buffer of the handle's own (starts at 1)             */
+#define NMF_VISNET_FRESH 5        /* [2] uint8                                                                 */
+void* nmf_visnet_field_ptr(nmf_visnet* visnet, int which, int32_t* width);
 
 /* Plume navigation with its state on the device (flygym_amd.controllers.PlumeNavigator; csrc/nmf_navigator.hip): a stochastic walk /
  * stop / turn state machine driven by odor onsets ("encounters"), in the form of Demir et al. 2020 as flygym 1.x steered its
