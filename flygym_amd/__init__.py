@@ -11,7 +11,7 @@ from .models import make_model
 
 assets_dir = Path(__file__).resolve().parent / "assets"     # as `flygym.assets_dir` (pose files; the asset pack)
 
-__all__ = ["anatomy", "compose", "make_model", "HIPSimulation", "Simulation"]
+__all__ = ["anatomy", "compose", "make_model", "HIPSimulation", "Simulation", "WalkingTask", "TaskEnv"]
 __version__ = "0.1.0"
 
 
@@ -24,4 +24,8 @@ def __getattr__(name):
         from .simulation import Simulation
 
         return Simulation
+    if name in ("WalkingTask", "TaskEnv"):
+        from . import tasks
+
+        return getattr(tasks, name)
     raise AttributeError(name)

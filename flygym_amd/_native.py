@@ -202,6 +202,12 @@ def lib():
             "nmf_visnet_reset": (ci, [vp, vp, vp]),
             "nmf_visnet_update": (ci, [vp, vp, vp, vp, vp]),
             "nmf_visnet_field_ptr": (vp, [vp, ci, ctypes.POINTER(ctypes.c_int32)]),
+            "nmf_task_params_size": (ctypes.c_size_t, []),
+            "nmf_task_create": (vp, [vp, vp, vp, vp, vp, vp, vp]),
+            "nmf_task_destroy": (None, [vp]),
+            "nmf_task_reset": (ci, [vp, vp, vp]),
+            "nmf_task_update": (ci, [vp, vp]),
+            "nmf_task_field_ptr": (vp, [vp, ci, ctypes.POINTER(ctypes.c_int32)]),
             "nmf_navigator_params_size": (ctypes.c_size_t, []),
             "nmf_navigator_create": (vp, [vp, vp]),
             "nmf_navigator_destroy": (None, [vp]),

@@ -20,9 +20,9 @@
 #include "nmf_step.hip"
 #include "nmf_sensors.hip"
 // `#pragma clang fp reassociate(off)` at file scope holds from the first file that sets it to the end of the translation unit:
-// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip, nmf_plume.hip, nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip, nmf_navigator.hip, nmf_stabilizer.hip, nmf_rules.hip, nmf_visnet.hip and the host code
+// nmf_scene.h (through nmf_eyes.hip) sets it, so nmf_camera.hip, nmf_replay.hip, nmf_cpg.hip, nmf_plume.hip, nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip, nmf_navigator.hip, nmf_stabilizer.hip, nmf_rules.hip, nmf_visnet.hip, nmf_task.hip and the host code
 // below are all compiled under it, and the files above are not.  Which files it covers decides their kernels' arithmetic: keep the
-// order (nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip, nmf_navigator.hip, nmf_stabilizer.hip, nmf_rules.hip and nmf_visnet.hip add pragmas inside their functions only: nothing of them reaches past the file).
+// order (nmf_taxis.hip, nmf_odometry.hip, nmf_motion.hip, nmf_navigator.hip, nmf_stabilizer.hip, nmf_rules.hip, nmf_visnet.hip and nmf_task.hip add pragmas inside their functions only: nothing of them reaches past the file).
 #include "nmf_eyes.hip"
 #include "nmf_camera.hip"
 #include "nmf_replay.hip"
@@ -35,6 +35,7 @@
 #include "nmf_stabilizer.hip"
 #include "nmf_rules.hip"
 #include "nmf_visnet.hip"
+#include "nmf_task.hip"
 #include "nmf_skeleton.h"      // nmf_model, the blob parser, classify_skeleton
 #endif
 
@@ -67,7 +68,7 @@ struct DeviceGuard {
   DeviceGuard guard_((b)->mem.device);                                                        \
   if (guard_.err != hipSuccess) return fail(std::string("hipSetDevice: ") + hipGetErrorString(guard_.err))
 
-// The device memory of one handle (batch, eye plan, camera plan, CPG, plume, odometry, motion, navigator, stabilizer, rules, visual network): every allocation is 16-byte granular, recorded, and freed
+// The device memory of one handle (batch, eye plan, camera plan, CPG, plume, odometry, motion, navigator, stabilizer, rules, visual network, task): every allocation is 16-byte granular, recorded, and freed
 // with the handle.  The first failure sets the error text, named after the entry point `who`, and sticks: later calls return
 // null without touching the device, so that a caller tests `ok` once after its last allocation.
 struct DevMem {
@@ -1905,6 +1906,134 @@ extern "C" int nmf_visnet_update(nmf_visnet* V, const float* omm_dev, const floa
   HIP_OK(hipGetLastError());
   hipLaunchKernelGGL(nmf::nmf_visnet_world_kernel, dim3((unsigned)((V->n_worlds + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      V->args, V->ptrs, base_dev, drive_out_dev);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// ---- the walking task (nmf_task.hip) ----
+// The per-world arrays and the handle's tables; the batch lends its pose, velocity, force, sensor and joint-angle arrays to every update.
+struct nmf_task {
+  int n_worlds = 0;
+  nmf::TaskArgs args{};
+  nmf::TaskPtrs ptrs{};
+  DevMem mem;
+};
+
+extern "C" size_t nmf_task_params_size(void) { return sizeof(nmf_task_params); }
+
+extern "C" void nmf_task_destroy(nmf_task* T) {
+  if (!T) return;
+  T->mem.release();
+  delete T;
+}
+
+extern "C" int nmf_task_reset(nmf_task* T, const uint8_t* mask_dev, void* stream) {
+  if (!T) return fail("nmf_task_reset: null task");
+  DEVICE_GUARD(T);
+  hipLaunchKernelGGL(nmf::nmf_task_reset_kernel, dim3((unsigned)((T->n_worlds + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     T->args, T->ptrs, mask_dev);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+static int fill_task(nmf_task* T, const nmf_batch* b, const nmf_task_params* p, const int32_t* act, const int32_t* act_dof,
+                     const int32_t* obs_dof, const float* mean, const float* inv_std) {
+  const std::string who = "nmf_task_create: ";
+  if (p->n_act < 1 || p->n_act > NMF_TASK_MAX_ACT) return fail(who + "n_act must be in 1..64, got " + std::to_string(p->n_act));
+  if (p->n_q < 1 || p->n_q > NMF_TASK_MAX_Q) return fail(who + "n_q must be in 1..256, got " + std::to_string(p->n_q));
+  const float values[21] = {p->cos_max_tilt, p->z_min, p->z_max, p->arena[0], p->arena[1], p->arena[2], p->arena[3], p->goal_radius2,
+                            p->power_clip, p->thr2[0], p->thr2[1], p->thr2[2], p->thr2[3], p->thr2[4], p->thr2[5], p->alive,
+                            p->w_progress, p->w_power, p->w_tilt, p->bonus_goal, p->penalty_fail};
+  for (float v : values)
+    if (!std::isfinite(v)) return fail(who + "a parameter is not finite");
+  for (int k = 0; k < p->n_q; ++k)
+    if (!std::isfinite(mean[k]) || !std::isfinite(inv_std[k])) return fail(who + "mean or inv_std is not finite at input " + std::to_string(k));
+  const int nseg = b->model->nseg, n_dof = b->model->nq - 7, nu = b->model->nu;
+  if (p->root_seg < 0 || p->root_seg >= nseg) return fail(who + "root_seg " + std::to_string(p->root_seg) + " is outside the batch's " + std::to_string(nseg) + " segments");
+  for (int a = 0; a < p->n_act; ++a) {
+    if (act[a] < 0 || act[a] >= nu)
+      return fail(who + "act[" + std::to_string(a) + "] = " + std::to_string(act[a]) + " is outside the model's " + std::to_string(nu) + " controls (nu)");
+    if (act_dof[a] < 0 || act_dof[a] >= n_dof)
+      return fail(who + "act_dof[" + std::to_string(a) + "] = " + std::to_string(act_dof[a]) + " is outside the model's " + std::to_string(n_dof) + " joint dofs");
+  }
+  for (int k = 0; k < p->n_q; ++k)
+    if (obs_dof[k] < 0 || obs_dof[k] >= n_dof)
+      return fail(who + "obs_dof[" + std::to_string(k) + "] = " + std::to_string(obs_dof[k]) + " is outside the model's " + std::to_string(n_dof) + " joint dofs");
+  if (p->tilt_ticks < 1) return fail(who + "tilt_ticks must be at least 1, got " + std::to_string(p->tilt_ticks));
+  if (p->airborne_ticks < 1) return fail(who + "airborne_ticks must be at least 1, got " + std::to_string(p->airborne_ticks));
+  if (p->max_ticks < 1) return fail(who + "max_ticks must be at least 1, got " + std::to_string(p->max_ticks));
+  if (p->grace_ticks < 0) return fail(who + "grace_ticks must not be negative, got " + std::to_string(p->grace_ticks));
+  if (p->cos_max_tilt < -1.f || p->cos_max_tilt > 1.f) return fail(who + "cos_max_tilt must be in [-1, 1]");
+  if (p->z_min > p->z_max) return fail(who + "z_min > z_max");
+  if (!(p->arena[0] < p->arena[1]) || !(p->arena[2] < p->arena[3])) return fail(who + "the arena is empty: it takes x_min < x_max and y_min < y_max");
+  if (p->goal_radius2 < 0.f) return fail(who + "goal_radius2 must not be negative");
+  for (int l = 0; l < 6; ++l)
+    if (p->thr2[l] < 0.f) return fail(who + "thr2 must not be negative at leg " + std::to_string(l));
+  // the int32 power sum: n_act terms of at most rint(power_clip 2^k)
+  const double top = std::nearbyint((double)(p->power_clip * (float)(1 << NMF_TASK_POWER_BITS)));
+  if (p->power_clip < 0.f || top * (double)p->n_act > 2147483647.0)
+    return fail(who + "power_clip must be in 0.." + std::to_string(2147483647.0 / (double)p->n_act / (double)(1 << NMF_TASK_POWER_BITS)) +
+                " for " + std::to_string(p->n_act) + " actuators (the power sum is an int32 in units of 2^-" + std::to_string(NMF_TASK_POWER_BITS) + ")");
+  if (b->model->nsensor == 0 || !b->st.sensordata || b->widths[NMF_SENSORDATA] != 96)
+    return fail(who + "the contact flags need six leg sensors of 16 values, the batch's sensordata is " + std::to_string(b->widths[NMF_SENSORDATA]) + " wide");
+  nmf::TaskArgs& A = T->args;
+  A.p = *p;
+  A.n_worlds = T->n_worlds; A.nseg = nseg; A.nq = b->widths[NMF_QPOS]; A.nv = b->widths[NMF_QVEL]; A.nu = b->widths[NMF_ACTUATOR_FORCE];
+  A.sens_stride = b->widths[NMF_SENSORDATA]; A.obs_width = NMF_TASK_OBS_BODY + 6 + p->n_q;
+  const size_t n = (size_t)T->n_worlds;
+  nmf::TaskPtrs& P = T->ptrs;
+  P.seg_xpos = b->st.seg_xpos; P.seg_xquat = b->st.seg_xquat; P.qpos = b->st.qpos; P.qvel = b->st.qvel;
+  P.actuator_force = b->st.actuator_force; P.sensordata = b->st.sensordata;
+  P.act = (const int*)T->mem.upload(act, sizeof(int) * (size_t)p->n_act);
+  P.act_dof = (const int*)T->mem.upload(act_dof, sizeof(int) * (size_t)p->n_act);
+  P.obs_dof = (const int*)T->mem.upload(obs_dof, sizeof(int) * (size_t)p->n_q);
+  P.mean = (const float*)T->mem.upload(mean, sizeof(float) * (size_t)p->n_q);
+  P.inv_std = (const float*)T->mem.upload(inv_std, sizeof(float) * (size_t)p->n_q);
+  P.reward = (float*)T->mem.alloc(sizeof(float) * n);
+  P.obs = (float*)T->mem.alloc(sizeof(float) * n * (size_t)A.obs_width);
+  P.ep_return = (float*)T->mem.alloc(sizeof(float) * n);
+  P.last_return = (float*)T->mem.alloc(sizeof(float) * n);
+  P.prev_xy = (float*)T->mem.alloc(sizeof(float) * 2 * n);
+  std::vector<float> course(2 * n, 0.f);
+  for (size_t w = 0; w < n; ++w) course[2 * w] = 1.f;
+  P.course = (float*)T->mem.upload(course.data(), sizeof(float) * 2 * n);
+  P.goal = (float*)T->mem.alloc(sizeof(float) * 2 * n);
+  P.terminated = (uint8_t*)T->mem.alloc(n); P.truncated = (uint8_t*)T->mem.alloc(n);
+  P.done = (uint8_t*)T->mem.alloc(n); P.fresh = (uint8_t*)T->mem.alloc(n);
+  int** words[8] = {&P.reason, &P.ep_length, &P.last_length, &P.last_reason, &P.tilt_count, &P.airborne_count, &P.episodes, &P.successes};
+  for (int** slot : words) *slot = (int*)T->mem.alloc(sizeof(int) * n);
+  if (!T->mem.ok) return -1;
+  if (nmf_task_reset(T, nullptr, nullptr) != 0) return -1;
+  HIP_OK(hipDeviceSynchronize());
+  return 0;
+}
+
+extern "C" nmf_task* nmf_task_create(nmf_batch* b, const nmf_task_params* p, const int32_t* act, const int32_t* act_dof,
+                                     const int32_t* obs_dof, const float* mean, const float* inv_std) {
+  if (!b || !p || !act || !act_dof || !obs_dof || !mean || !inv_std) { fail("nmf_task_create: null batch / params / act / act_dof / obs_dof / mean / inv_std"); return nullptr; }
+  return build_or_destroy(b->mem.device, "nmf_task_create", new nmf_task(), nmf_task_destroy, [&](nmf_task* T) {
+    T->n_worlds = b->n_worlds;
+    return fill_task(T, b, p, act, act_dof, obs_dof, mean, inv_std);
+  });
+}
+
+extern "C" void* nmf_task_field_ptr(nmf_task* T, int which, int32_t* width) {
+  if (!T) { fail("nmf_task_field_ptr: null task"); return nullptr; }
+  const nmf::TaskPtrs& P = T->ptrs;
+  void* ptr[NMF_TASK_FIELD_COUNT] = {P.reward, P.obs, P.ep_return, P.last_return, P.prev_xy, P.course, P.goal, P.terminated, P.truncated, P.done,
+                                     P.fresh, P.reason, P.ep_length, P.last_length, P.last_reason, P.tilt_count, P.airborne_count, P.episodes,
+                                     P.successes};
+  if (which < 0 || which >= NMF_TASK_FIELD_COUNT) { fail("nmf_task_field_ptr: no such field"); return nullptr; }
+  if (width) *width = which == NMF_TASK_OBS ? T->args.obs_width : (which >= NMF_TASK_PREV_XY && which <= NMF_TASK_GOAL_XY) ? 2 : 1;
+  return ptr[which];
+}
+
+// Pure stream-ordered work: one kernel launch.
+extern "C" int nmf_task_update(nmf_task* T, void* stream) {
+  if (!T) return fail("nmf_task_update: null task");
+  DEVICE_GUARD(T);
+  hipLaunchKernelGGL(nmf::nmf_task_update_kernel, dim3((unsigned)((T->n_worlds + nmf::kTaskWorlds - 1) / nmf::kTaskWorlds)), dim3(nmf::kTaskThreads),
+                     0, (hipStream_t)stream, T->args, T->ptrs);
   HIP_OK(hipGetLastError());
   return 0;
 }

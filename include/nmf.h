@@ -34,6 +34,7 @@ typedef struct nmf_navigator nmf_navigator;
 typedef struct nmf_stabilizer nmf_stabilizer;
 typedef struct nmf_rules nmf_rules;
 typedef struct nmf_visnet nmf_visnet;
+typedef struct nmf_task nmf_task;
 
 /* Per-world fields addressable through nmf_field_ptr / nmf_gather_* */
 enum nmf_field {
@@ -1055,6 +1056,124 @@ void* nmf_rules_field_ptr(nmf_rules* rules, int which, int32_t* width);
  * (the counters and the tick words live on the device, so a captured launch continues and draws afresh on every replay).
  * Refused: what nmf_cpg_advance refuses. */
 int nmf_rules_advance(nmf_rules* rules, int n_steps, float* table_dev, int table_steps, void* stream);
+
+/* The walking task on the device (flygym_amd.tasks.WalkingTask; csrc/nmf_task.hip): what an episode is, when it ends, what a tick
+ * was worth and which worlds start again -- the layer flygym 1.x's Gymnasium environments (`step` -> obs, reward, terminated,
+ * truncated, info, with flip detection) put around a walking fly.  No reference counterpart (the snapshot holds no tasks):
+ * build-defined and pinned by nothing, and nothing is claimed about matching flygym 1.x (specification
+ * tests/task_spec.py).  One update (one launch per control tick) reads, as they stand when the launch starts,
+ *   from the batch:  (x, y, z) = seg_xpos[root_seg], (qw, qx, qy, qz) = seg_xquat[root_seg];  qvel[0:3] = (vx, vy, vz), the root's
+ *     linear velocity in the WORLD frame, and qvel[3:6] = (ox, oy, oz), its angular velocity in the BODY frame (MuJoCo's free joint:
+ *     the step integrates position += h qvel[0:3] and quat <- quat * exp(h qvel[3:6] / 2));  f_a = actuator_force[act[a]] and
+ *     qd_a = qvel[6 + act_dof[a]], a < n_act;  of sensordata, per leg l the four floats (found, Fx, Fy, Fz) at [16 l .. 16 l + 3];
+ *     ang_k = qpos[7 + obs_dof[k]], k < n_q
+ *   from the handle:  course[w] = (cx, cy), a unit direction the host normalised, and goal[w] = (gx, gy)
+ * and, per world, does the following.  Everything is float32, every operation is rounded on its own (no contraction, no
+ * reassociation; fl() marks a rounding that matters), every clamp and every test is a comparison (false for a NaN), every stored
+ * float that is a zero is +0, the counters are int32 that wrap, and `old` state is the state before the update.
+ *   1. bad = one of the values just listed has all exponent bits set (NaN, +Inf, -Inf; tested on the bits).  A bad world gets
+ *      reason = NONFINITE alone, reward = -penalty_fail exactly and an observation row of zeros; steps 2 to 6 decide nothing for it.
+ *   2. progress = fresh ? 0 : fl(fl(fl(x - px) cx) + fl(fl(y - py) cy)),  (px, py) = prev_xy: the root's position at the last update
+ *   3. up_z = fl(1 - fl(2 fl(fl(qx qx) + fl(qy qy))))  (the z component of the body's z axis);
+ *      tilt_count <- up_z < cos_max_tilt ? tilt_count + 1 : 0
+ *   4. flag_l = found_l > 0 and fl(fl(fl(Fx Fx) + fl(Fy Fy)) + fl(Fz Fz)) > thr2[l];  airborne_count <- no flag set ? airborne_count + 1 : 0
+ *   5. P = sum_a (int32) rint(c_a 2^NMF_TASK_POWER_BITS),  c_a = |fl(f_a qd_a)| clamped: c < 0 ? 0 : (c > power_clip ? power_clip : c)
+ *      (an int32 sum: the same whatever the order; a term whose f_a or qd_a is not finite is 0, so nothing that is not finite is
+ *      converted);  power = (float) P 2^-NMF_TASK_POWER_BITS  (the conversion rounds to nearest even)
+ *   6. n = ep_length + 1;  grace = n <= grace_ticks;  reason = the bits
+ *        TILTED when not grace and tilt_count >= tilt_ticks;  AIRBORNE when not grace and airborne_count >= airborne_ticks (the new counts);
+ *        HEIGHT when not grace and (z < z_min or z > z_max);  OUT_OF_ARENA when x < arena[0] or x > arena[1] or y < arena[2] or y > arena[3];
+ *        GOAL when fl(fl(dx dx) + fl(dy dy)) < goal_radius2,  (dx, dy) = (fl(gx - x), fl(gy - y))  (goal_radius2 = 0: never)
+ *      terminated = reason != 0;  truncated = not terminated and n >= max_ticks;  done = terminated or truncated
+ *   7. r = alive;  r = fl(r + fl(w_progress progress));  r = fl(r - fl(w_power power));  r = fl(r - fl(w_tilt fl(1 - up_z)));
+ *      with GOAL r = fl(r + bonus_goal);  with any other bit r = fl(r - penalty_fail);  reward = r
+ *   8. ep_return <- fl(ep_return + reward);  ep_length <- n.  When done: last_return, last_length, last_reason <- ep_return, n, reason
+ *      (0: the time limit);  episodes += 1;  successes += 1 with GOAL;  ep_return, ep_length, tilt_count, airborne_count, prev_xy <- 0
+ *      and fresh <- 1: the kernel itself starts the next episode.  Otherwise prev_xy <- (x, y), fresh <- 0.
+ *   9. obs[w], NMF_TASK_OBS_BODY + 6 + n_q wide.  With the rotation R (body to world) of the unit quaternion, every entry rounded
+ *        r00 = fl(1 - fl(2 fl(qy qy + qz qz)))  r01 = fl(2 fl(qx qy - qw qz))          r02 = fl(2 fl(qx qz + qw qy))
+ *        r10 = fl(2 fl(qx qy + qw qz))          r11 = fl(1 - fl(2 fl(qx qx + qz qz)))  r12 = fl(2 fl(qy qz - qw qx))
+ *        r20 = fl(2 fl(qx qz - qw qy))          r21 = fl(2 fl(qy qz + qw qx))          r22 = up_z
+ *      (each product inside rounded first), the row is
+ *        [0:3]   -r20, -r21, -r22                                               the direction of gravity in the body frame
+ *        [3:6]   fl(fl(fl(r0j vx) + fl(r1j vy)) + fl(r2j vz)),  j = 0, 1, 2     the linear velocity in the body frame
+ *        [6:9]   ox, oy, oz                                                     the angular velocity (already in the body frame)
+ *        [9:11]  fl(fl(r0j dx) + fl(r1j dy)),  j = 0, 1                         (goal - position, 0) in the body frame, x and y
+ *        [11]    z
+ *        [12:18] flag_l as 0 / 1
+ *        [18:]   fl(fl(ang_k - mean[k]) inv_std[k])                             (the stabilizer's standardisation; inv_std from the host)
+ * No square root, no division and no function call: the library's fast-math licences cannot reach the rule (csrc/nmf_exact.h). */
+#define NMF_TASK_NONFINITE 1
+#define NMF_TASK_TILTED 2
+#define NMF_TASK_AIRBORNE 4
+#define NMF_TASK_HEIGHT 8
+#define NMF_TASK_OUT_OF_ARENA 16
+#define NMF_TASK_GOAL 32
+#define NMF_TASK_POWER_BITS 10      /* k of step 5: the power sum counts in units of 2^-10                                        */
+#define NMF_TASK_MAX_ACT 64
+#define NMF_TASK_MAX_Q 256
+#define NMF_TASK_OBS_BODY 12        /* the body-level floats at the start of an observation row                                   */
+typedef struct nmf_task_params {
+  int32_t root_seg;             /* index of the body's root segment in the batch's segment order                                  */
+  int32_t n_act, n_q;           /* actuators of the power sum (1..NMF_TASK_MAX_ACT), joint dofs observed (1..NMF_TASK_MAX_Q)       */
+  int32_t tilt_ticks, airborne_ticks, max_ticks;   /* each >= 1                                                                    */
+  int32_t grace_ticks;          /* >= 0: the first updates of an episode that raise no TILTED, AIRBORNE or HEIGHT                  */
+  float cos_max_tilt;           /* in [-1, 1]                                                                                      */
+  float z_min, z_max;           /* z_min <= z_max                                                                                  */
+  float arena[4];               /* x_min, x_max, y_min, y_max with x_min < x_max and y_min < y_max                                 */
+  float goal_radius2;           /* the goal disc's radius squared (>= 0; 0: no goal)                                               */
+  float power_clip;             /* >= 0, and n_act rint(power_clip 2^NMF_TASK_POWER_BITS) must fit an int32                        */
+  float thr2[6];                /* per leg: the squared force above which a touching leg counts (>= 0)                             */
+  float alive, w_progress, w_power, w_tilt, bonus_goal, penalty_fail;
+} nmf_task_params;
+
+/* sizeof(nmf_task_params) as this library was compiled (as nmf_eye_params_size). */
+size_t nmf_task_params_size(void);
+
+/* An explicit handle for the worlds of `batch`, on its device.  act[n_act] are actuator indices, act_dof[n_act] and obs_dof[n_q]
+ * joint dofs (0 = the first after the free joint), mean[n_q] and inv_std[n_q] the standardisation: host arrays, copied.  Owns the
+ * per-world arrays and resets every world (nmf_task_reset with a NULL mask); course starts at (1, 0), goal at (0, 0).  NOT
+ * stream-ordered (allocations); must not be called inside a stream capture.  NULL on error (nmf_last_error), with nothing left
+ * allocated: a null pointer; n_act outside 1..64 or n_q outside 1..256; a parameter, mean or inv_std that is not finite; root_seg,
+ * an actuator or a dof outside the model; tilt_ticks, airborne_ticks or max_ticks below 1; grace_ticks below 0; cos_max_tilt outside
+ * [-1, 1]; z_min > z_max; an empty arena; goal_radius2 or a thr2 below 0; a power_clip that is negative or lets the power sum
+ * overflow; a batch without the six leg sensors; no device memory.  The handle keeps pointers to the batch's arrays: destroy it
+ * before the batch. */
+nmf_task* nmf_task_create(nmf_batch* batch, const nmf_task_params* params, const int32_t* act, const int32_t* act_dof,
+                          const int32_t* obs_dof, const float* mean, const float* inv_std);
+void nmf_task_destroy(nmf_task* task);
+
+/* The worlds with mask_dev[w] != 0 (uint8 per world, device memory; NULL: all) get every array below zeroed except course and
+ * goal, and fresh = 1: a new episode and empty statistics.  The others are not touched.  Stream-ordered. */
+int nmf_task_reset(nmf_task* task, const uint8_t* mask_dev, void* stream);
+
+/* One update of every world: argument checks and ONE kernel launch on `stream`, no allocation, no host synchronisation,
+ * hipGraph-capturable (all state lives on the device, so a captured update continues on every replay).  NMF_TASK_DONE is the mask
+ * nmf_reset_worlds and every handle's reset take.  Refused: a null handle. */
+int nmf_task_update(nmf_task* task, void* stream);
+
+/* Device pointer + row width of an array of the handle (zero-copy views; writable between launches). */
+#define NMF_TASK_REWARD 0           /* [1] float32                                                             */
+#define NMF_TASK_OBS 1              /* [12 + 6 + n_q] float32                                                  */
+#define NMF_TASK_EP_RETURN 2        /* [1] float32                                                             */
+#define NMF_TASK_LAST_RETURN 3      /* [1] float32                                                             */
+#define NMF_TASK_PREV_XY 4          /* [2] float32                                                             */
+#define NMF_TASK_COURSE 5           /* [2] float32: user-written, a unit direction                             */
+#define NMF_TASK_GOAL_XY 6          /* [2] float32: user-written                                               */
+#define NMF_TASK_TERMINATED 7       /* [1] uint8                                                               */
+#define NMF_TASK_TRUNCATED 8        /* [1] uint8                                                               */
+#define NMF_TASK_DONE 9             /* [1] uint8                                                               */
+#define NMF_TASK_FRESH 10           /* [1] uint8                                                               */
+#define NMF_TASK_REASON 11          /* [1] int32: the NMF_TASK_ bits above                                     */
+#define NMF_TASK_EP_LENGTH 12       /* [1] int32                                                               */
+#define NMF_TASK_LAST_LENGTH 13     /* [1] int32                                                               */
+#define NMF_TASK_LAST_REASON 14     /* [1] int32                                                               */
+#define NMF_TASK_TILT_COUNT 15      /* [1] int32                                                               */
+#define NMF_TASK_AIRBORNE_COUNT 16  /* [1] int32                                                               */
+#define NMF_TASK_EPISODES 17        /* [1] int32                                                               */
+#define NMF_TASK_SUCCESSES 18       /* [1] int32                                                               */
+#define NMF_TASK_FIELD_COUNT 19
+void* nmf_task_field_ptr(nmf_task* task, int which, int32_t* width);
 
 /* Odor intensity at n_sensors points rigidly attached to named segments (sensor_seg = index into the
  * batch's segment order, sensor_rel = offset in the segment frame): out[w][d][k] = sum_s peak[s][d] / dist^2.
